@@ -2,7 +2,7 @@
 """Benchmark of the ColorVideoVDP hot path on MI355X.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload 4k64|fhd64|4k256|4k1024|8k256pq] [--dtype f32|u8|yuv420p8|yuv420p10]
-                    [--heatmap none|raw|threshold|supra-threshold] [--distogram] [--gen cpu|gpu]
+                    [--heatmap none|raw|threshold|supra-threshold] [--distogram] [--gen cpu|gpu] [--full] [--dump-outputs DIR]
     python bench.py --gpus N ...            # N > 1 without a launcher: starts its own ranks through torch.distributed.run (self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -14,9 +14,14 @@ all-gather of Q_per_ch, pooling on every rank):
   * 4k1024 (configs[3]) and 8k256pq (configs[4], PQ, supra-threshold heat map streamed off the GPU + distogram): frames in
     TOTAL -- every rank scores 1/N of the clip (strong scaling).
 
-Prints ONE JSON line (rank 0).  value = Mpixel/s of the whole job = W*H*frames_scored_by_all_ranks*K / t.  With one GPU
-and a clip the real reference was run on (tests/golden/bench_*.npz, oracle/make_goldens_bench.py) the frames are made with
-the CPU generator the fixture was made with, and the line carries jod_delta_vs_reference of the very clip it times.
+Prints ONE JSON line (rank 0).  value = Mpixel/s of the whole job = W*H*frames_scored_by_all_ranks*K / t, ms_per_step = t / K.
+With one GPU and a clip the real reference was run on (tests/golden/bench_*.npz, oracle/make_goldens_bench.py) the frames are
+made with the CPU generator the fixture was made with.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline figure does not need: HIP-event
+kernel times inside the timed steps with the roofline figures built on them, clock / power under load, jod_delta_vs_reference of the
+very clip it times, the CPU baseline and, with several ranks, the all-gather timed alone.  --dump-outputs DIR writes what the last
+timed step returned as DIR/<name>.npy (the inputs are seeded: the same arguments give the same clip in every run).
 """
 import argparse
 import json
@@ -136,10 +141,10 @@ def cpu_frame_pool(frame_ids, H, W):
     torch operators on 25 M samples stop scaling at a handful of threads, so: many workers with four threads each).
     Returns (iterator, pool, torch thread count to restore after pool.shutdown())."""
     import concurrent.futures
-    ncpu = os.cpu_count() or 1
-    workers = max(1, min(32, ncpu // 4))
     threads_before = torch.get_num_threads()
-    torch.set_num_threads(max(1, min(threads_before, ncpu // workers)))
+    ncpu = max(1, threads_before)        # the CPUs this process may use (OMP_NUM_THREADS where it is set), not every CPU of the host
+    workers = max(1, min(32, ncpu // 4))
+    torch.set_num_threads(max(1, ncpu // workers))
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=workers)
     return pool.map(lambda f: synth_frame(f, H, W, "cpu"), frame_ids), pool, threads_before
 
@@ -422,6 +427,51 @@ def _capi_build_info():
     return _capi.build_info()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _float_array(v):
+    """A numeric output as a float32 / float64 numpy array (float16 and integers widen), None for anything else."""
+    if torch.is_tensor(v):
+        v = v.detach()
+        v = (v if v.dtype in (torch.float32, torch.float64) else v.double() if not v.is_floating_point() else v.float()).cpu().numpy()
+    elif isinstance(v, (float, np.floating)) or (isinstance(v, np.ndarray) and v.dtype.kind in "fiu"):
+        v = np.asarray(v)
+    else:
+        return None
+    if v.dtype.kind != "f":
+        return v.astype(np.float64)
+    return v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)
+
+
+def dump_outputs(path, jod, stats, sink=None, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the JOD, every numeric array of `stats` (Q_per_ch,
+    rho_band, a whole-clip heat map) and, with a heat-map sink, the sink's per-frame means ([frame, channel]) -- as <path>/<name>.npy in
+    float32 / float64.  An array larger than an even share of `limit` is written as a fixed sample of its flattened values (seed 0, the
+    same positions in every run), so that the files of two builds can be compared output for output.  Returns the names written."""
+    arrays = {"jod": jod if torch.is_tensor(jod) else np.asarray(jod)}
+    arrays.update((k, v) for k, v in stats.items() if torch.is_tensor(v) or isinstance(v, np.ndarray))
+    if sink is not None:
+        if hasattr(sink, "close"):
+            sink.close()                                  # a device sink fetches its means here
+        arrays["heatmap_frame_means"] = np.stack([sink.means[f] for f in sorted(sink.means)]) if sink.means else np.zeros((0, 3))
+    share = limit // max(len(arrays), 1)
+    os.makedirs(path, exist_ok=True)
+    written = []
+    for name, v in arrays.items():
+        n = int(v.numel() if torch.is_tensor(v) else v.size)
+        itemsize = 4 if str(v.dtype).endswith(("float32", "float16")) else 8          # as written: float16 widens to 4 bytes, integers to 8
+        if n * itemsize > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, share // itemsize))
+            flat = v.reshape(-1)
+            v = flat[torch.from_numpy(idx).to(flat.device)] if torch.is_tensor(v) else flat[idx]
+        a = _float_array(v)
+        if a is not None:
+            np.save(os.path.join(path, name + ".npy"), a)
+            written.append(name)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -445,7 +495,15 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=16, help="frames of the CPU baseline sample: a prefix of the workload clip (SURVEY 8d: 16; 0 = skip)")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-power-probe", action="store_true", help="skip the 1.6 s of untimed steps under rocm-smi after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: HIP-event kernel times and the roofline figures built "
+                         "on them, clock / power under load, the comparison with the reference fixture of the clip, the CPU baseline and, "
+                         "with several ranks, the all-gather timed alone (--no-profile, --no-power-probe and --cpu-frames 0 drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (JOD, Q_per_ch, rho_band, heat-map frame means) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -536,7 +594,8 @@ def main():
     torch.cuda.synchronize()
     if dist_on:
         torch.distributed.barrier()
-    if not args.no_profile:
+    profile = args.full and not args.no_profile      # HIP events around every kernel family, inside the timed steps
+    if profile:
         m.profile(True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -547,30 +606,33 @@ def main():
     if dist_on:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
-    prof = None if args.no_profile else m.profile_read()
+    prof = m.profile_read() if profile else None
     m.profile(False)
-    power = power_probe(step, torch.cuda.synchronize) if (world == 1 and not args.no_profile and not args.no_power_probe) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, jod, stats, sink)      # before anything else runs the step again
+    power = power_probe(step, torch.cuda.synchronize) if (world == 1 and profile and not args.no_power_probe) else None
     per_rank = None
     if dist_on:
         # what makes the first hardware SCALE line explain itself: every rank's own time for the K steps (the value
-        # uses the MAX of the barrier-to-barrier times, as the contract says), and the step's only collective timed on its own
+        # uses the MAX of the barrier-to-barrier times, as the contract says), and (--full) the step's only collective timed on its own
         gdev = device if backend == "nccl" else torch.device("cpu")
         mine = torch.tensor([dt, dt_own], device=gdev, dtype=torch.float64)
         allt = [torch.empty_like(mine) for _ in range(world)]
         torch.distributed.all_gather(allt, mine)
         per_rank = [[float(x[0]), float(x[1])] for x in allt]
         dt = max(x[0] for x in per_rank)
-        from colorvideovdp_amd.sharding import all_gather_frames
-        q_local = torch.zeros((1, 4, count, int(stats["Q_per_ch"].shape[-1])), dtype=torch.float32, device=device)
-        n_ag = 20
-        all_gather_frames(q_local, n_total)           # (first call: communicator / buffers)
-        torch.cuda.synchronize()
-        torch.distributed.barrier()
-        ta = time.perf_counter()
-        for _ in range(n_ag):
-            all_gather_frames(q_local, n_total)
-        torch.cuda.synchronize()
-        allgather_us = (time.perf_counter() - ta) / n_ag * 1e6
+        if args.full:
+            from colorvideovdp_amd.sharding import all_gather_frames
+            q_local = torch.zeros((1, 4, count, int(stats["Q_per_ch"].shape[-1])), dtype=torch.float32, device=device)
+            n_ag = 20
+            all_gather_frames(q_local, n_total)           # (first call: communicator / buffers)
+            torch.cuda.synchronize()
+            torch.distributed.barrier()
+            ta = time.perf_counter()
+            for _ in range(n_ag):
+                all_gather_frames(q_local, n_total)
+            torch.cuda.synchronize()
+            allgather_us = (time.perf_counter() - ta) / n_ag * 1e6
     if rank != 0:
         if dist_on:
             torch.distributed.destroy_process_group()
@@ -602,17 +664,18 @@ def main():
         out["config"]["collectives"] = {"backend": torch.distributed.get_backend(), "world": world,
                                         "per_step": "one all-gather of the Q_per_ch shards", "spin_up": "barrier + one broadcast word per step",
                                         "ranks_seen": ranks_seen, "distinct_devices": distinct,
-                                        "allgather_us": round(allgather_us, 1),
-                                        "allgather_note": f"the step's only collective ([1,4,{count},bands] fp32 per rank) timed alone, {n_ag} calls back to back "
-                                                          "after the timed region (host clock around synchronize)",
                                         "halo_frames_per_rank": halo,
                                         "halo_note": f"real frames before the shard that only pass through the temporal kernel (rank 0 pads instead); "
                                                      f"{fl - 1} of {count} = {(fl - 1) / max(count, 1):.1%} more frames to read and convert on ranks > 0"}
+        if args.full:
+            out["config"]["collectives"]["allgather_us"] = round(allgather_us, 1)
+            out["config"]["collectives"]["allgather_note"] = (f"the step's only collective ([1,4,{count},bands] fp32 per rank) timed alone, {n_ag} calls "
+                                                              "back to back after the timed region (host clock around synchronize)")
         out["per_rank_ms"] = [round(x[1] / args.steps * 1e3, 3) for x in per_rank]
         out["per_rank_ms_note"] = ("every rank's own K steps / K, before the closing barrier (ms_per_step is the MAX over ranks of the barrier-to-barrier "
                                    "time, as the contract says); the spread says which rank was slow, rank 0 carries no halo frames")
         out["config"]["per_rank_ms"] = out["per_rank_ms"]      # (the driver's record keeps `config`; unknown top-level keys only by name)
-    if golden is not None and gen == "cpu":
+    if args.full and golden is not None and gen == "cpu":
         if (clip.checksum_test, clip.checksum_ref) == (int(golden["checksum_test"]), int(golden["checksum_ref"])):
             q, qr = stats["Q_per_ch"].astype(np.float64), golden["Q_per_ch"].astype(np.float64)
             out["jod_reference"] = round(float(golden["jod"]), 5)
@@ -628,23 +691,24 @@ def main():
         else:
             out["jod_delta_vs_reference"] = None      # this torch build's CPU generator does not reproduce the fixture's frames
     fused_levels = m.fused_levels
+    out["config"]["fused_levels"] = fused_levels    # leading pyramid levels whose band kernel computes the next level itself (no reduce pass)
     stage_b = stage_bytes_per_pixel(dtype, fused_levels)
     surv, build = PATH_BYTES_PER_PIXEL[dtype], sum(stage_b.values())
-    out["config"]["fused_levels"] = fused_levels    # leading pyramid levels whose band kernel computes the next level itself (no reduce pass)
-    out["path_roofline"] = {
-        "survey_model": {"bytes_per_pixel": surv, "achieved_GBs": round(surv * pixels / dt / 1e9 / world, 1),
-                         "frac_of_8TBs_per_gpu": round(surv * pixels / dt / 1e9 / world / HBM_PEAK_GBS, 4),
-                         "note": "SURVEY.md 8(d): includes a 48 B/pixel DKL ring this design does not have and reads every level twice"},
-        "build_algorithmic": {"bytes_per_pixel": round(build, 1), "achieved_GBs": round(build * pixels / dt / 1e9 / world, 1),
-                              "frac_of_8TBs_per_gpu": round(build * pixels / dt / 1e9 / world / HBM_PEAK_GBS, 4),
-                              "note": "fewer algorithmic bytes than round 2 (162.6 for f32): fused band kernels read a level once, so the "
-                                      "same pixel rate is a smaller fraction" if fused_levels > 0 else "no fused levels for this clip"},
-    }
-    ceil = measured_copy_ceiling(build * W * H * count / 2 / 1e6)      # bytes read ~ bytes written per step: one "side" of a copy
-    if ceil is not None:
-        for k in ("survey_model", "build_algorithmic"):
-            out["path_roofline"][k]["frac_of_measured_copy_per_gpu"] = round(out["path_roofline"][k]["achieved_GBs"] / ceil["GBs"], 4)
-        out["path_roofline"]["measured_copy_ceiling"] = ceil
+    if args.full:
+        out["path_roofline"] = {
+            "survey_model": {"bytes_per_pixel": surv, "achieved_GBs": round(surv * pixels / dt / 1e9 / world, 1),
+                             "frac_of_8TBs_per_gpu": round(surv * pixels / dt / 1e9 / world / HBM_PEAK_GBS, 4),
+                             "note": "SURVEY.md 8(d): includes a 48 B/pixel DKL ring this design does not have and reads every level twice"},
+            "build_algorithmic": {"bytes_per_pixel": round(build, 1), "achieved_GBs": round(build * pixels / dt / 1e9 / world, 1),
+                                  "frac_of_8TBs_per_gpu": round(build * pixels / dt / 1e9 / world / HBM_PEAK_GBS, 4),
+                                  "note": "fewer algorithmic bytes than round 2 (162.6 for f32): fused band kernels read a level once, so the "
+                                          "same pixel rate is a smaller fraction" if fused_levels > 0 else "no fused levels for this clip"},
+        }
+        ceil = measured_copy_ceiling(build * W * H * count / 2 / 1e6)      # bytes read ~ bytes written per step: one "side" of a copy
+        if ceil is not None:
+            for k in ("survey_model", "build_algorithmic"):
+                out["path_roofline"][k]["frac_of_measured_copy_per_gpu"] = round(out["path_roofline"][k]["achieved_GBs"] / ceil["GBs"], 4)
+            out["path_roofline"]["measured_copy_ceiling"] = ceil
     if prof is not None:
         ms, n = prof["band_level0"]
         frames_per_launch = count * args.steps / max(n, 1)
@@ -742,7 +806,7 @@ def main():
         except Exception as e:   # matplotlib is optional on the box
             out["distogram_bytes"] = None
             out["distogram_error"] = repr(e)
-    if args.cpu_frames > 0 and world == 1:
+    if args.full and args.cpu_frames > 0 and world == 1:
         cb, ojod, t, r = cpu_baseline(W, H, fps, display, args.cpu_frames)
         out["cpu_baseline"] = cb
         hjod, _ = cv.cvvdp(display_name=display, device=device).predict(t, r, dim_order="BCFHW", frames_per_second=fps)

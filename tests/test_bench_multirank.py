@@ -62,7 +62,7 @@ def test_two_rank_bench_prints_its_line_every_time(workload, extra, frames_total
 def test_eight_rank_dry_run_explains_itself(workload, extra, frames_total):
     """the line the driver's first 8-GPU run will print, dry-run with eight ranks on the one GPU of the box (gloo):
     eight per-rank times (not only their MAX), the step's only collective timed on its own, the halo frames every rank reads."""
-    d = _bench_two_ranks(["--workload", workload] + extra, 30300 + (os.getpid() % 1500), world=8, timeout=600)
+    d = _bench_two_ranks(["--workload", workload, "--full"] + extra, 30300 + (os.getpid() % 1500), world=8, timeout=600)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["frames_total"] == frames_total
     assert len(d["per_rank_ms"]) == 8 and all(t > 0 for t in d["per_rank_ms"]) and d["config"]["per_rank_ms"] == d["per_rank_ms"]
     assert max(d["per_rank_ms"]) <= d["ms_per_step"] * 1.001                  # the value is priced on the barrier-to-barrier MAX

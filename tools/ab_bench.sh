@@ -5,7 +5,7 @@ TAG=${1:-ab}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 WL=${WORKLOAD:-4k64}
 run() { # name, lib
-  CVVDP_DEV_KNOBS=1 CVVDP_LIB=$2 timeout 600 python bench.py --workload $WL --steps 10 --warmup 3 --cpu-frames 0 --no-power-probe $BENCH_ARGS > $OUT/$1.json 2> $OUT/$1.err
+  CVVDP_DEV_KNOBS=1 CVVDP_LIB=$2 timeout 600 python bench.py --full --workload $WL --steps 10 --warmup 3 --cpu-frames 0 --no-power-probe $BENCH_ARGS > $OUT/$1.json 2> $OUT/$1.err
   python - "$OUT/$1.json" "$1" <<'PY'
 import json,sys
 try:

@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 i=0
 for setting in "$@"; do
   i=$((i+1))
-  env CVVDP_DEV_KNOBS=1 CVVDP_LIB=$PWD/colorvideovdp_amd/libcvvdp_hip_dev.so $setting timeout 900 python bench.py --steps 10 --warmup 3 --cpu-frames 0 --no-power-probe $ARGS > $OUT/$i.json 2> $OUT/$i.err
+  env CVVDP_DEV_KNOBS=1 CVVDP_LIB=$PWD/colorvideovdp_amd/libcvvdp_hip_dev.so $setting timeout 900 python bench.py --full --steps 10 --warmup 3 --cpu-frames 0 --no-power-probe $ARGS > $OUT/$i.json 2> $OUT/$i.err
   python - "$OUT/$i.json" "$setting" <<'PY'
 import json,sys
 try:

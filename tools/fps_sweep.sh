@@ -6,7 +6,7 @@ for lib in "" "$@"; do
   name=$(basename ${lib:-intree} .so)
   for dt in f32 u8; do
     for fps in 24 30 60 90 120; do
-      CVVDP_DEV_KNOBS=1 CVVDP_LIB=${lib:+$PWD/$lib} timeout 300 python bench.py --fps $fps --dtype $dt --steps 5 --warmup 2 --cpu-frames 0 > $OUT/${name}_${dt}_$fps.json 2>/dev/null
+      CVVDP_DEV_KNOBS=1 CVVDP_LIB=${lib:+$PWD/$lib} timeout 300 python bench.py --full --fps $fps --dtype $dt --steps 5 --warmup 2 --cpu-frames 0 > $OUT/${name}_${dt}_$fps.json 2>/dev/null
       python - "$OUT/${name}_${dt}_$fps.json" "$name $dt $fps" <<'PY'
 import json,sys
 try:
