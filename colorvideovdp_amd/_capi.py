@@ -12,7 +12,7 @@ MAX_WINDOW = 256
 CSF_NODES = 32
 PROF_N = 6
 PROF_NAMES = ("photometry", "temporal_fir", "pyr_reduce", "band_level0", "band_rest", "heatmap")
-ABI_VERSION = 13
+ABI_VERSION = 14
 RESIZE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2, "area": 3}   # CVVDP_RESIZE_*
 
 U8, U16, F16, F32, F32_DKL, YUV8, YUV16 = range(7)
@@ -70,6 +70,19 @@ class YuvFormat(C.Structure):
     ]
 
 
+PSNR_AS_IS, PSNR_PU21, PSNR_Y, PSNR_RGB2020 = range(4)   # CVVDP_PSNR_*
+
+
+class PsnrArgs(C.Structure):
+    _fields_ = [
+        ("target", C.c_int32), ("reserved", C.c_int32),
+        ("pu_p", C.c_float * 7),
+        ("pu_L_min", C.c_float), ("pu_L_max", C.c_float),
+        ("pu_norm", C.c_float),
+        ("rows", C.c_float * 9),
+    ]
+
+
 SYMBOLS = {
     "cvvdp_abi_version": (C.c_int, []),
     "cvvdp_build_flags": (C.c_int, []),
@@ -91,6 +104,11 @@ SYMBOLS = {
                                           C.c_int32, C.c_int32, C.c_void_p]),
     "cvvdp_unpack_yuv_resized": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cvvdp_psnr_args_size": (C.c_int32, []),
+    "cvvdp_pixel_sse_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cvvdp_pixel_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(YuvFormat),
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PsnrArgs), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_process_block_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.c_int32, C.c_int32, C.c_void_p]),
     "cvvdp_get_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -140,6 +158,8 @@ def lib():
         l.cvvdp_struct_sizes(C.byref(sp), C.byref(sc))
         if (sp.value, sc.value) != (C.sizeof(Params), C.sizeof(Clip)):
             raise ImportError(f"struct layout mismatch: library {(sp.value, sc.value)} vs binding {(C.sizeof(Params), C.sizeof(Clip))}")
+        if l.cvvdp_psnr_args_size() != C.sizeof(PsnrArgs):
+            raise ImportError(f"struct layout mismatch: cvvdp_psnr_args is {l.cvvdp_psnr_args_size()} bytes in the library, {C.sizeof(PsnrArgs)} in the binding")
         # The band kernels' hand-issued loads were checked against the register allocation of the compiler the library was built with
         # (cvvdp_build_info; bench.py prints it in config.library_build).  The HIP runtime in the process is whatever torch's wheel
         # bundles (here 7.0 under a 7.2 toolchain: a minor-version gap is the normal state and says nothing), so only another MAJOR

@@ -1,7 +1,8 @@
 """Command line of the MI355X build: `python -m colorvideovdp_amd` / `cvvdp` (console entry in pyproject.toml).
 
 Mirrors the reference's command line (pycvvdp/run_cvvdp.py:83-118 arguments, :120-371 run_on_args) for the path this build
-implements: the `cvvdp` metric on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit), planar .yuv clips (the
+implements: the `cvvdp` metric and the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020` (`-m cvvdp psnr-rgb ...`, one output
+line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit), planar .yuv clips (the
 file name carries size, frame rate, bit depth and chroma format, video_source_yuv.py:8-62) and .npy arrays.  Same options,
 same output lines (`cvvdp=9.1234 [JOD]`, or only the number with --quiet), same side outputs (--result CSV, --features
 JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpeg and the build is GPU-only:
@@ -9,12 +10,14 @@ JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpe
   * the heat map of a VIDEO is streamed block by block: into `<base>_heatmap.mp4` through an ffmpeg pipe (the reference's
     file and codec settings) where an `ffmpeg` executable exists, otherwise into a numbered PNG sequence
     `<base>_heatmap_%05d.png` (`ffmpeg -i <base>_heatmap_%05d.png <base>_heatmap.mp4` converts it); an image gives `<base>_heatmap.png`;
-  * --device must be a cuda device; --temp-padding 'valid', --temp-resample, --dump-channels and metrics other than cvvdp are
-    not available; --full-screen-resize works for .yuv clips (as in the reference it is not implemented for images).
+  * --device must be a cuda device; --temp-padding 'valid', --temp-resample, --dump-channels and the metrics the reference does not
+    register by default (SSIM, dm-preview, the cvvdp-ml heads) are not available; --full-screen-resize works for .yuv clips (as in the
+    reference it is not implemented for images).
 Clips stored as numbered image frames work as in the reference: `-t t_%04d.png -r r_%04d.png --fps 30 [--frames 10:2:50]`.
 """
 import argparse
 import glob
+import inspect
 import logging
 import os
 import shlex
@@ -26,6 +29,7 @@ import torch
 
 from . import heatmap_writers
 from .cvvdp_metric import cvvdp
+from . import psnr_metric  # noqa: F401  (registers psnr_rgb, pu_psnr_y, pu_psnr_rgb2020)
 from .display_model import vvdp_display_geometry, vvdp_display_photometry
 from .video_source_file import IMAGE_EXT, VIDEO_EXT, load_image_as_array, video_source_file
 from .vq_metric import vq_exception, vq_metric_dict
@@ -60,7 +64,7 @@ _OPTIONS = (
     (("--count-frames",), dict(action="store_true", default=False, help="accepted for compatibility (frame counts of .yuv / .npy inputs are exact)")),
     (("-f", "--full-screen-resize"), dict(choices=["bilinear", "bicubic", "nearest", "area"], default=None,
                                           help="resize test and reference to the display's resolution (.yuv clips; on the GPU, torch.nn.functional.interpolate semantics)")),
-    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s); this build registers cvvdp")),
+    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, psnr-rgb, pu-psnr-y, pu-psnr-rgb2020")),
     (("--temp-padding",), dict(choices=["replicate", "symmetric", "valid"], default="symmetric", help="padding before the first frame ('valid': " + _NA + ")")),
     (("--pix-per-deg",), dict(type=float, default=None, help="override the display geometry")),
     (("--fps",), dict(type=float, default=None, help="frame rate: needed for .npy clips and numbered image frames (name_%%04d.png), overrides a .yuv file name")),
@@ -103,6 +107,14 @@ def parse_frame_range(spec):
         if ss[kk].isnumeric():
             sn[kk] = int(ss[kk])
     return range(sn[0], sn[2] + 1, sn[1]) if len(ss) == 3 else range(sn[0], sn[1] + 1)
+
+
+def metric_arguments(metric_class, **available):
+    """The constructor arguments a metric accepts, out of `available` (run_cvvdp.py:244-270).  Only the signature of the constructor
+    that runs counts: the reference also collects its bases' argument names, which hands pu_psnr_rgb2020 (no config_paths) the
+    config_paths of pu_psnr_y and makes `-m pu-psnr-rgb2020` fail with a TypeError."""
+    names = set(inspect.getfullargspec(metric_class.__init__)[0])
+    return {k: v for k, v in available.items() if k in names}
 
 
 def run_on_args(args):
@@ -159,8 +171,9 @@ def run_on_args(args):
     for mm in args.metric:
         if mm not in vq_metric_dict:
             raise RuntimeError(f"Unknown metric {mm}")
-        fv = vq_metric_dict[mm](display_photometry=display_photometry, display_geometry=display_geometry, device=device, heatmap=args.heatmap,
-                                temp_padding=args.temp_padding, config_paths=args.config_paths, gpu_mem=args.gpu_mem, quiet=args.quiet)
+        fv = vq_metric_dict[mm](**metric_arguments(vq_metric_dict[mm], display_photometry=display_photometry, display_geometry=display_geometry,
+                                                   device=device, heatmap=args.heatmap, temp_padding=args.temp_padding,
+                                                   config_paths=args.config_paths, gpu_mem=args.gpu_mem, quiet=args.quiet))
         fv.train(False)
         metrics.append(fv)
         info = fv.get_info_string()
@@ -185,7 +198,7 @@ def run_on_args(args):
                 mm.set_base_fname(os.path.join(out_dir, base))
                 is_video = vs.get_video_size()[2] > 1
                 sink = None
-                if args.heatmap and is_video:          # streamed to disk block by block: bounded host memory at any clip length
+                if args.heatmap and is_video and getattr(mm, "do_heatmap", False):          # streamed to disk block by block: bounded host memory at any clip length
                     if heatmap_writers.HeatmapVideoWriter.available():     # the reference's file (run_cvvdp.py:349-354)
                         dest = os.path.join(out_dir, base + "_heatmap.mp4")
                         logging.info(f"Writing heat map '{dest}' ...")

@@ -777,6 +777,57 @@ int cvvdp_unpack_yuv_resized(cvvdp_handle* h, const void* codes, const cvvdp_yuv
   return check_launch(h, "yuv resize");
 }
 
+}  // extern "C"
+
+// cvvdp_pixel_sse (psnr.hip) up to the launch: argument checks and the kernel arguments.  The entry point itself lives next to its
+// kernels, so that this file references no symbol of them.
+int cvvdp::psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
+                        const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_psnr_args* args,
+                        const double* sse, const void* scratch, size_t scratch_bytes, PsnrArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!t || !r || !args || !sse || !scratch) return fail(h, CVVDP_E_ARG, "pixel_sse: null argument");
+  if (B < 1 || B > 65535 || n_frames < 1 || n_frames > 65535 || H < 1 || W < 1 || (C != 1 && C != 3))
+    return fail(h, CVVDP_E_ARG, "pixel_sse: bad geometry B=%d C=%d frames=%d %dx%d", B, C, n_frames, W, H);
+  if ((int64_t)H * W > 0x7fff0000) return fail(h, CVVDP_E_ARG, "pixel_sse: frame of %dx%d too large", W, H);
+  if (args->target < CVVDP_PSNR_AS_IS || args->target > CVVDP_PSNR_RGB2020) return fail(h, CVVDP_E_ARG, "pixel_sse: target %d unknown", args->target);
+  if (scratch_bytes < (size_t)B * n_frames * psnr_tiles(H, W) * sizeof(double)) return fail(h, CVVDP_E_ARG, "pixel_sse: scratch too small");
+  a = PsnrArgs{};
+  a.src[0] = t; a.src[1] = r;
+  a.dtype = dtype; a.target = args->target;
+  a.H = H; a.W = W; a.C = C; a.batch = B; a.n_frames = n_frames;
+  a.n_tiles = psnr_tiles(H, W);
+  if (dtype == CVVDP_YUV8 || dtype == CVVDP_YUV16) {
+    if (B != 1 || C != 3) return fail(h, CVVDP_E_ARG, "pixel_sse: Y'CbCr frames need B = 1 and C = 3");
+    if (!yuv) return fail(h, CVVDP_E_ARG, "pixel_sse: Y'CbCr format missing");
+    if ((yuv->bit_depth == 8) != (dtype == CVVDP_YUV8)) return fail(h, CVVDP_E_ARG, "pixel_sse: dtype and bit depth disagree");
+    if (int rc = fill_yuv(h, yuv, W, H, a.yuv)) return rc;
+    a.sf[0] = yuv->frame_stride_test; a.sf[1] = yuv->frame_stride_ref;
+  } else if (dtype >= CVVDP_U8 && dtype <= CVVDP_F32) {
+    if (!st || !sr) return fail(h, CVVDP_E_ARG, "pixel_sse: strides missing");
+    const int64_t* S[2] = {st, sr};
+    for (int k = 0; k < 2; ++k) { a.sb[k] = S[k][0]; a.sc[k] = S[k][1]; a.sf[k] = S[k][2]; a.sh[k] = S[k][3]; a.sw[k] = S[k][4]; }
+    // 16-sample row runs with 16-byte loads (psnr.hip load_row_run): whole runs in a row; element offsets in multiples of 16 and
+    // 16-byte aligned bases keep every run start 16-byte aligned
+    bool v16 = W % 16 == 0;
+    for (int k = 0; k < 2; ++k)
+      v16 = v16 && a.sw[k] == 1 && a.sh[k] % 16 == 0 && (C == 1 || a.sc[k] % 16 == 0) && a.sf[k] % 16 == 0 && a.sb[k] % 16 == 0 &&
+            reinterpret_cast<uintptr_t>(a.src[k]) % 16 == 0;
+    a.vec16 = v16 ? 1 : 0;
+  } else {
+    return fail(h, CVVDP_E_UNSUPPORTED, "pixel_sse: dtype %d unsupported", dtype);
+  }
+  fill_display(h, a.dm);
+  a.dm.channels = C;
+  for (int i = 0; i < 7; ++i) a.pu[i] = args->pu_p[i];
+  a.pu_lo = args->pu_L_min; a.pu_hi = args->pu_L_max; a.pu_norm = args->pu_norm;
+  for (int i = 0; i < 9; ++i) a.m[i] = args->rows[i];
+  a.partial = static_cast<double*>(const_cast<void*>(scratch));
+  return CVVDP_OK;
+}
+int cvvdp::psnr_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_sse"); }
+
+extern "C" {
+
 static int process_block_impl(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
                               const cvvdp::YuvArgs* yuv, int32_t raw_first, const int32_t* hist_src, int32_t n_frames,
                               int32_t q_frame_offset, void* stream) {

@@ -303,4 +303,28 @@ void launch_heat_colour(const HeatArgs& a, hipStream_t s);
 constexpr int kHeatStatsWords = 4 + 1024;
 constexpr int kHeatCurveWords = 1024 + 4;
 
+// ---------------------------------------------------------------- PSNR metrics (psnr.hip)
+struct PsnrArgs {
+  const void* src[2];       // test, ref
+  int64_t sb[2], sc[2], sf[2], sh[2], sw[2];  // element strides (Y'CbCr: sf = frame stride, the rest unused)
+  int32_t dtype, target;    // CVVDP_U8 .. CVVDP_F32, CVVDP_YUV8 / 16; CVVDP_PSNR_*
+  int32_t H, W, C, batch, n_frames;
+  int32_t n_tiles;          // psnr_tiles(H, W)
+  int32_t vec16;            // every row run of 16 samples can be read with 16-byte loads (W % 16 == 0, strides and pointers aligned)
+  DisplayArgs dm;
+  YuvArgs yuv;
+  float pu[7], pu_lo, pu_hi, pu_norm;   // cvvdp_psnr_args
+  float m[9];
+  double* partial;          // [frame][batch][tile]
+};
+static_assert(sizeof(PsnrArgs) <= 4096, "kernel arguments of the PSNR kernels");
+constexpr int kPsnrTilePx = 256 * 16;      // pixels per workgroup of k_psnr_sse (256 threads x 16 pixels)
+inline int psnr_tiles(int H, int W) { return (int)(((int64_t)H * W + kPsnrTilePx - 1) / kPsnrTilePx); }
+// core.cpp: argument checks and kernel arguments of cvvdp_pixel_sse; the error of a launch
+int psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
+                 const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_psnr_args* args,
+                 const double* sse, const void* scratch, size_t scratch_bytes, PsnrArgs& a);
+int psnr_check_launch(cvvdp_handle* h);
+void launch_psnr_sse(const PsnrArgs& a, double* sse, double* mse_acc, hipStream_t s);
+
 }  // namespace cvvdp

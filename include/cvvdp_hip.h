@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define CVVDP_ABI_VERSION 13
+#define CVVDP_ABI_VERSION 14
 #define CVVDP_MAX_FILTER_LEN 65 /* 0.25 s at up to 256 fps, cvvdp_metric.py:1059 */
 #define CVVDP_MAX_LEVELS 16
 #define CVVDP_MAX_WINDOW 256    /* filter_len - 1 + frames per block */
@@ -60,7 +60,7 @@ enum {
 
 /* input sample formats, video_source.py:320-346 */
 enum { CVVDP_U8 = 0, CVVDP_U16 = 1, CVVDP_F16 = 2, CVVDP_F32 = 3, CVVDP_F32_DKL = 4 /* already DKL-d65, fp32 */,
-       /* planar Y'CbCr frames, video_source_yuv.py:79-223; only through cvvdp_process_block_yuv */
+       /* planar Y'CbCr frames, video_source_yuv.py:79-223; only through cvvdp_process_block_yuv and cvvdp_pixel_sse */
        CVVDP_YUV8 = 5, CVVDP_YUV16 = 6 };
 /* EOTFs, display_model.py:333-365 */
 enum { CVVDP_EOTF_SRGB = 0, CVVDP_EOTF_PQ = 1, CVVDP_EOTF_HLG = 2, CVVDP_EOTF_LINEAR = 3, CVVDP_EOTF_GAMMA = 4 };
@@ -234,6 +234,41 @@ enum { CVVDP_RESIZE_NEAREST = 0, CVVDP_RESIZE_BILINEAR = 1, CVVDP_RESIZE_BICUBIC
 int cvvdp_unpack_yuv_resized(cvvdp_handle* h, const void* dev_codes, const cvvdp_yuv_format* fmt, int32_t is_ref, int32_t src_width,
                              int32_t src_height, int32_t n_frames, int32_t dst_width, int32_t dst_height, int32_t mode, float* dev_tmp,
                              float* dev_rgb, void* stream);
+
+/* PSNR metrics (pycvvdp/psnr_metric.py): psnr_rgb (:15-55), pu_psnr_y (:60-112), pu_psnr_rgb2020 (:115-123).  Per frame the reference
+ * converts both frames with the source's display model (video_source.py:320-346, display_model.py:206-273) and adds
+ * mean((T - R)^2 over C, H, W) to mse[b] (psnr_metric.py:36-43, :82-92).  cvvdp_pixel_sse does that for n_frames frames in one pass:
+ *   dev_test/dev_ref  samples (dtype CVVDP_U8 .. CVVDP_F32 with element strides in B,C,F,H,W order, a broadcast batch has stride 0), or
+ *                     planar Y'CbCr frames (dtype CVVDP_YUV8 / CVVDP_YUV16, yuv = their format as for cvvdp_process_block_yuv, B = 1,
+ *                     C = 3; the strides are not read)
+ *   dev_sse           double [n_frames][B]: sum over C, H, W of the squared difference in the target space
+ *   dev_mse_acc       double [B] or NULL: in frame order, mse_acc[b] += sse[f][b] / (n_out * H * W), n_out = 1 for CVVDP_PSNR_Y and C
+ *                     otherwise -- the reference's running mse, the same bits however a clip is cut into calls
+ *   dev_scratch       cvvdp_pixel_sse_scratch_bytes(B, n_frames, H, W) bytes of device memory
+ * Squares are summed in fp32 over 16 pixels, then in double in an order that depends only on H and W (no atomics).  The handle
+ * supplies the display model (cvvdp_create from a cvvdp_params whose display fields are filled); no clip needs to be configured. */
+enum {
+  CVVDP_PSNR_AS_IS = 0,    /* the samples as they are: display-encoded values (display_model.py:209-211, not clamped), or frames a source
+                              has already converted to the metric's colour space (any channel count C) */
+  CVVDP_PSNR_PU21 = 1,     /* PU.encode(forward(V)) / PU.encode(100) per channel: psnr_rgb on linear and PQ displays (display_model.py:212-226) */
+  CVVDP_PSNR_Y = 2,        /* rows[0..2] . forward(V) (display_model.py:246), forward(V) for C = 1 */
+  CVVDP_PSNR_RGB2020 = 3   /* rows (3x3) . forward(V) (display_model.py:259-273), forward(V) for C = 1 */
+};
+typedef struct cvvdp_psnr_args {
+  int32_t target;          /* CVVDP_PSNR_* */
+  int32_t reserved;
+  float pu_p[7];           /* PU21 'banding_glare' parameters as fp32 (utils.py:190-205) */
+  float pu_L_min, pu_L_max;/* the clip of PU.encode, 0.005 and 10000 */
+  float pu_norm;           /* CVVDP_PSNR_PU21: fp32 PU.encode(100) */
+  float rows[9];           /* CVVDP_PSNR_Y: fp32 rgb2xyz[1,:] in rows[0..2]; CVVDP_PSNR_RGB2020: fp32 XYZ_to_RGB2020 @ rgb2xyz, row-major */
+} cvvdp_psnr_args;
+size_t cvvdp_pixel_sse_scratch_bytes(int32_t B, int32_t n_frames, int32_t H, int32_t W);
+int cvvdp_pixel_sse(cvvdp_handle* h, const void* dev_test, const void* dev_ref, int32_t dtype, const int64_t strides_test[5],
+                    const int64_t strides_ref[5], const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W,
+                    const cvvdp_psnr_args* args, double* dev_sse, double* dev_mse_acc, void* dev_scratch, size_t scratch_bytes,
+                    void* stream);
+/* sizeof(cvvdp_psnr_args) as compiled. */
+int32_t cvvdp_psnr_args_size(void);
 
 /* Sources that deliver temporally pre-filtered channels (vid_source.is_temporally_filtered, cvvdp_metric.py:470-488):
  * frames are fp32 [B, 4, n, H, W] in colour space 'DKLd65_trans' (Y-sustained, RG, YV, Y-transient; element strides in
