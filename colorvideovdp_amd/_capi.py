@@ -83,6 +83,21 @@ class PsnrArgs(C.Structure):
     ]
 
 
+SSIM_WIN = 11   # CVVDP_SSIM_WIN
+
+
+class SsimArgs(C.Structure):
+    _fields_ = [
+        ("target", C.c_int32), ("reserved", C.c_int32),
+        ("win", C.c_float * SSIM_WIN),
+        ("C1", C.c_float), ("C2", C.c_float),
+        ("luma", C.c_float * 3),
+        ("pu_p", C.c_float * 7),
+        ("pu_L_min", C.c_float), ("pu_L_max", C.c_float),
+        ("pu_norm", C.c_float),
+    ]
+
+
 SYMBOLS = {
     "cvvdp_abi_version": (C.c_int, []),
     "cvvdp_build_flags": (C.c_int, []),
@@ -109,6 +124,11 @@ SYMBOLS = {
     "cvvdp_pixel_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(YuvFormat),
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PsnrArgs), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_ssim_args_size": (C.c_int32, []),
+    "cvvdp_pixel_ssim_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cvvdp_pixel_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(YuvFormat),
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SsimArgs), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_process_block_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.c_int32, C.c_int32, C.c_void_p]),
     "cvvdp_get_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -160,6 +180,8 @@ def lib():
             raise ImportError(f"struct layout mismatch: library {(sp.value, sc.value)} vs binding {(C.sizeof(Params), C.sizeof(Clip))}")
         if l.cvvdp_psnr_args_size() != C.sizeof(PsnrArgs):
             raise ImportError(f"struct layout mismatch: cvvdp_psnr_args is {l.cvvdp_psnr_args_size()} bytes in the library, {C.sizeof(PsnrArgs)} in the binding")
+        if l.cvvdp_ssim_args_size() != C.sizeof(SsimArgs):
+            raise ImportError(f"struct layout mismatch: cvvdp_ssim_args is {l.cvvdp_ssim_args_size()} bytes in the library, {C.sizeof(SsimArgs)} in the binding")
         # The band kernels' hand-issued loads were checked against the register allocation of the compiler the library was built with
         # (cvvdp_build_info; bench.py prints it in config.library_build).  The HIP runtime in the process is whatever torch's wheel
         # bundles (here 7.0 under a 7.2 toolchain: a minor-version gap is the normal state and says nothing), so only another MAJOR

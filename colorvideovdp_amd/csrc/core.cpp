@@ -779,31 +779,33 @@ int cvvdp_unpack_yuv_resized(cvvdp_handle* h, const void* codes, const cvvdp_yuv
 
 }  // extern "C"
 
-// cvvdp_pixel_sse (psnr.hip) up to the launch: argument checks and the kernel arguments.  The entry point itself lives next to its
-// kernels, so that this file references no symbol of them.
-int cvvdp::psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
-                        const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_psnr_args* args,
-                        const double* sse, const void* scratch, size_t scratch_bytes, PsnrArgs& a) {
+// cvvdp_pixel_sse (psnr.hip) and cvvdp_pixel_ssim (ssim.hip) up to the launch: argument checks and the kernel arguments.  The entry
+// points themselves live next to their kernels, so that this file references no symbol of them.  `what` names the entry in messages;
+// n_tiles is its number of double partials per (frame, batch).
+static int pixel_prepare(const char* what, int n_tiles, cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5],
+                         const int64_t sr[5], const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W,
+                         const cvvdp_psnr_args* args, const double* sse, const void* scratch, size_t scratch_bytes, cvvdp::PsnrArgs& a) {
+  using namespace cvvdp;
   if (!h) return CVVDP_E_STATE;
-  if (!t || !r || !args || !sse || !scratch) return fail(h, CVVDP_E_ARG, "pixel_sse: null argument");
+  if (!t || !r || !args || !sse || !scratch) return fail(h, CVVDP_E_ARG, "%s: null argument", what);
   if (B < 1 || B > 65535 || n_frames < 1 || n_frames > 65535 || H < 1 || W < 1 || (C != 1 && C != 3))
-    return fail(h, CVVDP_E_ARG, "pixel_sse: bad geometry B=%d C=%d frames=%d %dx%d", B, C, n_frames, W, H);
-  if ((int64_t)H * W > 0x7fff0000) return fail(h, CVVDP_E_ARG, "pixel_sse: frame of %dx%d too large", W, H);
-  if (args->target < CVVDP_PSNR_AS_IS || args->target > CVVDP_PSNR_RGB2020) return fail(h, CVVDP_E_ARG, "pixel_sse: target %d unknown", args->target);
-  if (scratch_bytes < (size_t)B * n_frames * psnr_tiles(H, W) * sizeof(double)) return fail(h, CVVDP_E_ARG, "pixel_sse: scratch too small");
+    return fail(h, CVVDP_E_ARG, "%s: bad geometry B=%d C=%d frames=%d %dx%d", what, B, C, n_frames, W, H);
+  if ((int64_t)H * W > 0x7fff0000) return fail(h, CVVDP_E_ARG, "%s: frame of %dx%d too large", what, W, H);
+  if (args->target < CVVDP_PSNR_AS_IS || args->target > CVVDP_PSNR_RGB2020) return fail(h, CVVDP_E_ARG, "%s: target %d unknown", what, args->target);
+  if (scratch_bytes < (size_t)B * n_frames * n_tiles * sizeof(double)) return fail(h, CVVDP_E_ARG, "%s: scratch too small", what);
   a = PsnrArgs{};
   a.src[0] = t; a.src[1] = r;
   a.dtype = dtype; a.target = args->target;
   a.H = H; a.W = W; a.C = C; a.batch = B; a.n_frames = n_frames;
-  a.n_tiles = psnr_tiles(H, W);
+  a.n_tiles = n_tiles;
   if (dtype == CVVDP_YUV8 || dtype == CVVDP_YUV16) {
-    if (B != 1 || C != 3) return fail(h, CVVDP_E_ARG, "pixel_sse: Y'CbCr frames need B = 1 and C = 3");
-    if (!yuv) return fail(h, CVVDP_E_ARG, "pixel_sse: Y'CbCr format missing");
-    if ((yuv->bit_depth == 8) != (dtype == CVVDP_YUV8)) return fail(h, CVVDP_E_ARG, "pixel_sse: dtype and bit depth disagree");
+    if (B != 1 || C != 3) return fail(h, CVVDP_E_ARG, "%s: Y'CbCr frames need B = 1 and C = 3", what);
+    if (!yuv) return fail(h, CVVDP_E_ARG, "%s: Y'CbCr format missing", what);
+    if ((yuv->bit_depth == 8) != (dtype == CVVDP_YUV8)) return fail(h, CVVDP_E_ARG, "%s: dtype and bit depth disagree", what);
     if (int rc = fill_yuv(h, yuv, W, H, a.yuv)) return rc;
     a.sf[0] = yuv->frame_stride_test; a.sf[1] = yuv->frame_stride_ref;
   } else if (dtype >= CVVDP_U8 && dtype <= CVVDP_F32) {
-    if (!st || !sr) return fail(h, CVVDP_E_ARG, "pixel_sse: strides missing");
+    if (!st || !sr) return fail(h, CVVDP_E_ARG, "%s: strides missing", what);
     const int64_t* S[2] = {st, sr};
     for (int k = 0; k < 2; ++k) { a.sb[k] = S[k][0]; a.sc[k] = S[k][1]; a.sf[k] = S[k][2]; a.sh[k] = S[k][3]; a.sw[k] = S[k][4]; }
     // 16-sample row runs with 16-byte loads (psnr.hip load_row_run): whole runs in a row; element offsets in multiples of 16 and
@@ -814,7 +816,7 @@ int cvvdp::psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t d
             reinterpret_cast<uintptr_t>(a.src[k]) % 16 == 0;
     a.vec16 = v16 ? 1 : 0;
   } else {
-    return fail(h, CVVDP_E_UNSUPPORTED, "pixel_sse: dtype %d unsupported", dtype);
+    return fail(h, CVVDP_E_UNSUPPORTED, "%s: dtype %d unsupported", what, dtype);
   }
   fill_display(h, a.dm);
   a.dm.channels = C;
@@ -824,6 +826,39 @@ int cvvdp::psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t d
   a.partial = static_cast<double*>(const_cast<void*>(scratch));
   return CVVDP_OK;
 }
+int cvvdp::psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
+                        const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_psnr_args* args,
+                        const double* sse, const void* scratch, size_t scratch_bytes, PsnrArgs& a) {
+  const int n_tiles = H >= 1 && W >= 1 && (int64_t)H * W <= 0x7fff0000 ? psnr_tiles(H, W) : 0;
+  return pixel_prepare("pixel_sse", n_tiles, h, t, r, dtype, st, sr, yuv, B, C, n_frames, H, W, args, sse, scratch, scratch_bytes, a);
+}
+// cvvdp_pixel_ssim: the checks of cvvdp_pixel_sse on the same frames, then the window and the map's tiling
+int cvvdp::ssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
+                        const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_ssim_args* args,
+                        const double* ssim, const void* scratch, size_t scratch_bytes, SsimArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!args) return fail(h, CVVDP_E_ARG, "pixel_ssim: null argument");
+  if (args->target != CVVDP_PSNR_AS_IS && args->target != CVVDP_PSNR_PU21)
+    return fail(h, CVVDP_E_ARG, "pixel_ssim: target %d is neither CVVDP_PSNR_AS_IS nor CVVDP_PSNR_PU21", args->target);
+  // ssim_metric.py:10 indexes channels 1 and 2: luma needs three channels
+  if (C != 3) return fail(h, CVVDP_E_ARG, "pixel_ssim: bad geometry C=%d, luma is taken from three channels", C);
+  cvvdp_psnr_args pa{};
+  pa.target = args->target;
+  for (int i = 0; i < 7; ++i) pa.pu_p[i] = args->pu_p[i];
+  pa.pu_L_min = args->pu_L_min; pa.pu_L_max = args->pu_L_max; pa.pu_norm = args->pu_norm;
+  a = SsimArgs{};
+  const int n_tiles = H >= 1 && W >= 1 ? ssim_tiles(H, W) : 0;
+  if (int rc = pixel_prepare("pixel_ssim", n_tiles, h, t, r, dtype, st, sr, yuv, B, C, n_frames, H, W, &pa, ssim, scratch, scratch_bytes, a.p))
+    return rc;
+  for (int i = 0; i < kSsimWin; ++i) a.win[i] = args->win[i];
+  a.C1 = args->C1; a.C2 = args->C2;
+  for (int i = 0; i < 3; ++i) a.luma[i] = args->luma[i];
+  a.Hm = ssim_map_size(H); a.Wm = ssim_map_size(W);
+  a.fv = H >= kSsimWin; a.fh = W >= kSsimWin;
+  a.tiles_x = ssim_tiles_x(W); a.tiles_y = ssim_tiles_y(H);
+  return CVVDP_OK;
+}
+int cvvdp::ssim_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_ssim"); }
 int cvvdp::psnr_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_sse"); }
 
 extern "C" {

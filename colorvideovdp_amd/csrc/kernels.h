@@ -327,4 +327,31 @@ int psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, c
 int psnr_check_launch(cvvdp_handle* h);
 void launch_psnr_sse(const PsnrArgs& a, double* sse, double* mse_acc, hipStream_t s);
 
+// ---------------------------------------------------------------- SSIM metric (ssim.hip)
+// A workgroup of kSsimCols threads owns kSsimCols adjacent input columns (one per thread) and walks down kSsimRows rows of the SSIM
+// map: kSsimCols - 10 map columns when the width is filtered, kSsimCols otherwise.
+constexpr int kSsimWin = CVVDP_SSIM_WIN;
+constexpr int kSsimCols = 256;
+constexpr int kSsimRows = 64;
+struct SsimArgs {
+  PsnrArgs p;               // sources, strides, display model, PU21 constants, target (CVVDP_PSNR_AS_IS or CVVDP_PSNR_PU21); partial = scratch
+  float win[kSsimWin];
+  float C1, C2;
+  float luma[3];
+  int32_t Hm, Wm;           // size of the SSIM map
+  int32_t fv, fh;           // the height / the width is filtered (>= kSsimWin samples), ssim.py:46-52
+  int32_t tiles_x, tiles_y; // p.n_tiles = tiles_x * tiles_y
+};
+static_assert(sizeof(SsimArgs) <= 4096, "kernel arguments of the SSIM kernel");
+inline int ssim_map_size(int n) { return n >= kSsimWin ? n - (kSsimWin - 1) : n; }
+inline int ssim_tiles_x(int W) { const int out = W >= kSsimWin ? kSsimCols - (kSsimWin - 1) : kSsimCols; return (ssim_map_size(W) + out - 1) / out; }
+inline int ssim_tiles_y(int H) { return (ssim_map_size(H) + kSsimRows - 1) / kSsimRows; }
+inline int ssim_tiles(int H, int W) { return ssim_tiles_x(W) * ssim_tiles_y(H); }
+// core.cpp: argument checks and kernel arguments of cvvdp_pixel_ssim; the error of a launch
+int ssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
+                 const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_ssim_args* args,
+                 const double* ssim, const void* scratch, size_t scratch_bytes, SsimArgs& a);
+int ssim_check_launch(cvvdp_handle* h);
+void launch_pixel_ssim(const SsimArgs& a, double* ssim, double* acc, hipStream_t s);
+
 }  // namespace cvvdp

@@ -60,7 +60,7 @@ enum {
 
 /* input sample formats, video_source.py:320-346 */
 enum { CVVDP_U8 = 0, CVVDP_U16 = 1, CVVDP_F16 = 2, CVVDP_F32 = 3, CVVDP_F32_DKL = 4 /* already DKL-d65, fp32 */,
-       /* planar Y'CbCr frames, video_source_yuv.py:79-223; only through cvvdp_process_block_yuv and cvvdp_pixel_sse */
+       /* planar Y'CbCr frames, video_source_yuv.py:79-223; only through cvvdp_process_block_yuv, cvvdp_pixel_sse and cvvdp_pixel_ssim */
        CVVDP_YUV8 = 5, CVVDP_YUV16 = 6 };
 /* EOTFs, display_model.py:333-365 */
 enum { CVVDP_EOTF_SRGB = 0, CVVDP_EOTF_PQ = 1, CVVDP_EOTF_HLG = 2, CVVDP_EOTF_LINEAR = 3, CVVDP_EOTF_GAMMA = 4 };
@@ -269,6 +269,39 @@ int cvvdp_pixel_sse(cvvdp_handle* h, const void* dev_test, const void* dev_ref, 
                     void* stream);
 /* sizeof(cvvdp_psnr_args) as compiled. */
 int32_t cvvdp_psnr_args_size(void);
+
+/* SSIM metric (pycvvdp/ssim_metric.py:37-52 on pycvvdp/third_party/ssim.py:11-102, :131-159).  Per frame the reference fetches test
+ * and reference in 'display_encoded_100nit' (display_model.py:208-226: the samples as they are, or PU21(forward(V)) / PU21(100) on
+ * linear and PQ displays), takes luma = (luma[0]*R + luma[1]*G) + luma[2]*B (ssim_metric.py:9-10), filters X, Y, X*X, Y*Y and X*Y with
+ * the separable window without padding, down the height and then along the width (ssim.py:44-52; a dimension shorter than the window
+ * is not filtered), forms the SSIM map (ssim.py:89-98) and takes its mean over the map and the batch (ssim.py:100, :158-159).
+ * cvvdp_pixel_ssim does that for n_frames frames in one pass; the arguments are those of cvvdp_pixel_sse, with
+ *   C                 3 (the reference indexes three channels)
+ *   dev_ssim          double [n_frames][B]: mean of the SSIM map of frame f, batch item b
+ *   dev_acc           double [1] or NULL: in frame order, acc += (sum over b of ssim[f][b]) / B -- the reference's running sum over
+ *                     frames (ssim_metric.py:49), the same bits however a clip is cut into calls
+ *   dev_scratch       cvvdp_pixel_ssim_scratch_bytes(B, n_frames, H, W) bytes: one double per (frame, batch, tile), the only global
+ *                     memory the pass writes besides its results
+ * Taps are accumulated in window order (tap 0 first), the vertical pass before the horizontal one; map values are summed in fp32 down
+ * a thread's column segment, then in double in an order that depends only on H and W (no atomics). */
+#define CVVDP_SSIM_WIN 11
+typedef struct cvvdp_ssim_args {
+  int32_t target;          /* CVVDP_PSNR_AS_IS or CVVDP_PSNR_PU21 */
+  int32_t reserved;
+  float win[CVVDP_SSIM_WIN];/* fp32 Gaussian window, sigma 1.5, normalised by its fp32 sum (ssim.py:19-23) */
+  float C1, C2;            /* (0.01 * data_range)^2, (0.03 * data_range)^2, data_range = 1 (ssim.py:81-82) */
+  float luma[3];           /* 0.212656, 0.715158, 0.072186 (ssim_metric.py:10) */
+  float pu_p[7];           /* as cvvdp_psnr_args */
+  float pu_L_min, pu_L_max;
+  float pu_norm;
+} cvvdp_ssim_args;
+size_t cvvdp_pixel_ssim_scratch_bytes(int32_t B, int32_t n_frames, int32_t H, int32_t W);
+int cvvdp_pixel_ssim(cvvdp_handle* h, const void* dev_test, const void* dev_ref, int32_t dtype, const int64_t strides_test[5],
+                     const int64_t strides_ref[5], const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W,
+                     const cvvdp_ssim_args* args, double* dev_ssim, double* dev_acc, void* dev_scratch, size_t scratch_bytes,
+                     void* stream);
+/* sizeof(cvvdp_ssim_args) as compiled. */
+int32_t cvvdp_ssim_args_size(void);
 
 /* Sources that deliver temporally pre-filtered channels (vid_source.is_temporally_filtered, cvvdp_metric.py:470-488):
  * frames are fp32 [B, 4, n, H, W] in colour space 'DKLd65_trans' (Y-sustained, RG, YV, Y-transient; element strides in
