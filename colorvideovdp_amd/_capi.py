@@ -98,6 +98,10 @@ class SsimArgs(C.Structure):
     ]
 
 
+# CVVDP_E_RGBE_*: what cvvdp_rgbe_header / cvvdp_rgbe_decode answer to a file they do not read
+RGBE_E_MAGIC, RGBE_E_XYZE, RGBE_E_ORIENTATION, RGBE_E_SIZE, RGBE_E_BUFFER, RGBE_E_TRUNCATED, RGBE_E_RUN, RGBE_E_SCANLINE_WIDTH, RGBE_E_ZERO_COUNT = \
+    range(-101, -110, -1)
+
 SYMBOLS = {
     "cvvdp_abi_version": (C.c_int, []),
     "cvvdp_build_flags": (C.c_int, []),
@@ -129,6 +133,10 @@ SYMBOLS = {
     "cvvdp_pixel_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(YuvFormat),
                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SsimArgs), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_rgbe_header": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "cvvdp_rgbe_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "cvvdp_rgbe_strerror": (C.c_char_p, [C.c_int]),
+    "cvvdp_unpack_rgbe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "cvvdp_process_block_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.c_int32, C.c_int32, C.c_void_p]),
     "cvvdp_get_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

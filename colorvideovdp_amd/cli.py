@@ -2,7 +2,7 @@
 
 Mirrors the reference's command line (pycvvdp/run_cvvdp.py:83-118 arguments, :120-371 run_on_args) for the path this build
 implements: the `cvvdp` metric, the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020` and the SSIM metric `ssim-metric`
-(`-m cvvdp psnr-rgb ssim-metric ...`, one output line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit), planar .yuv clips (the
+(`-m cvvdp psnr-rgb ssim-metric ...`, one output line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit; Radiance .hdr for HDR images, e.g. `-d standard_hdr_linear`), planar .yuv clips (the
 file name carries size, frame rate, bit depth and chroma format, video_source_yuv.py:8-62) and .npy arrays.  Same options,
 same output lines (`cvvdp=9.1234 [JOD]`, or only the number with --quiet), same side outputs (--result CSV, --features
 JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpeg and the build is GPU-only:
@@ -14,6 +14,8 @@ JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpe
     register by default (dm-preview, the cvvdp-ml heads) are not available; --full-screen-resize works for .yuv clips (as in the
     reference it is not implemented for images).
 Clips stored as numbered image frames work as in the reference: `-t t_%04d.png -r r_%04d.png --fps 30 [--frames 10:2:50]`.
+Radiance .hdr frames work the same way (`-t t_%04d.hdr -r r_%04d.hdr --fps 24`); test and reference must then both be .hdr.  OpenEXR
+files (.exr) are not read: store such frames as .hdr or as float32 .npy arrays.
 """
 import argparse
 import glob
@@ -51,7 +53,7 @@ def expand_wildcards(filestrs):
 # the contract existing scripts rely on; the help texts say what THIS build does with them.
 _NA = "not available in this build"
 _OPTIONS = (
-    (("-t", "--test"), dict(type=str, nargs="+", help="test images / clips (wildcards allowed)")),
+    (("-t", "--test"), dict(type=str, nargs="+", help="test images / clips (wildcards allowed): 8 / 16-bit images, Radiance .hdr, planar .yuv, .npy")),
     (("-r", "--ref"), dict(type=str, nargs="+", help="reference images / clips; one reference may serve many tests and vice versa")),
     (("--device",), dict(type=str, default="cuda", help="'cuda' or 'cuda:N' (there is no CPU path)")),
     (("--heatmap",), dict(type=str, default="none", help="difference map: none, raw, threshold or supra-threshold")),
@@ -68,7 +70,7 @@ _OPTIONS = (
     (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, psnr-rgb, pu-psnr-y, pu-psnr-rgb2020, ssim-metric")),
     (("--temp-padding",), dict(choices=["replicate", "symmetric", "valid"], default="symmetric", help="padding before the first frame ('valid': " + _NA + ")")),
     (("--pix-per-deg",), dict(type=float, default=None, help="override the display geometry")),
-    (("--fps",), dict(type=float, default=None, help="frame rate: needed for .npy clips and numbered image frames (name_%%04d.png), overrides a .yuv file name")),
+    (("--fps",), dict(type=float, default=None, help="frame rate: needed for .npy clips and numbered image frames (name_%%04d.png, name_%%04d.hdr), overrides a .yuv file name")),
     (("--frames",), dict(type=str, default=None, help="frames of an image sequence to use: first:step:last, first:last or first: (both ends included)")),
     (("--gpu-mem",), dict(type=float, default=None, help="GPU memory budget in GB")),
     (("-q", "--quiet"), dict(action="store_true", default=False, help="print the JOD value only")),

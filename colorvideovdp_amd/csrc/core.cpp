@@ -859,6 +859,24 @@ int cvvdp::ssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t d
   return CVVDP_OK;
 }
 int cvvdp::ssim_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_ssim"); }
+// cvvdp_unpack_rgbe (rgbe.hip) up to the launch
+int cvvdp::rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int32_t H, int32_t W, float* out, int64_t stride_c,
+                        int64_t stride_f, RgbeArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!rgbe || !out) return fail(h, CVVDP_E_ARG, "unpack_rgbe: null argument");
+  if (n_frames < 1 || n_frames > 65535 || H < 1 || W < 1) return fail(h, CVVDP_E_ARG, "unpack_rgbe: bad geometry frames=%d %dx%d", n_frames, W, H);
+  if ((int64_t)H * W > 0x7fff0000) return fail(h, CVVDP_E_ARG, "unpack_rgbe: frame of %dx%d too large", W, H);
+  const int64_t HW = (int64_t)H * W;
+  if (stride_c < HW || stride_f < HW) return fail(h, CVVDP_E_ARG, "unpack_rgbe: stride shorter than a plane of %dx%d", W, H);
+  if (reinterpret_cast<uintptr_t>(rgbe) % 4 || reinterpret_cast<uintptr_t>(out) % 4) return fail(h, CVVDP_E_ARG, "unpack_rgbe: pointer not 4-byte aligned");
+  a = RgbeArgs{};
+  a.src = static_cast<const uint32_t*>(rgbe); a.dst = out;
+  a.sc = stride_c; a.sf = stride_f; a.HW = (int32_t)HW; a.n_frames = n_frames;
+  a.all_vec = HW % 4 == 0 && stride_c % 4 == 0 && stride_f % 4 == 0 && reinterpret_cast<uintptr_t>(rgbe) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(out) % 16 == 0;
+  return CVVDP_OK;
+}
+int cvvdp::rgbe_check_launch(cvvdp_handle* h) { return check_launch(h, "unpack_rgbe"); }
 int cvvdp::psnr_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_sse"); }
 
 extern "C" {

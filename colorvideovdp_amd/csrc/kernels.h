@@ -354,4 +354,20 @@ int ssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, c
 int ssim_check_launch(cvvdp_handle* h);
 void launch_pixel_ssim(const SsimArgs& a, double* ssim, double* acc, hipStream_t s);
 
+// ---------------------------------------------------------------- Radiance RGBE frames (rgbe.hip)
+// n_frames frames of uint8 [H][W][4] (R, G, B, E), packed back to back -> fp32 planes: channel c of frame f at dst + c * sc + f * sf.
+constexpr int kRgbeThreads = 256;
+struct RgbeArgs {
+  const uint32_t* src;      // one 32-bit word per pixel: R | G << 8 | B << 16 | E << 24
+  float* dst;
+  int64_t sc, sf;           // floats between channels / frames of dst
+  int32_t HW, n_frames;
+  int32_t all_vec;          // every frame starts 16-byte aligned on both sides and H * W is a multiple of 4: the grid covers pixel quads
+};
+// core.cpp: argument checks and kernel arguments of cvvdp_unpack_rgbe; the error of a launch
+int rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int32_t H, int32_t W, float* out, int64_t stride_c, int64_t stride_f,
+                 RgbeArgs& a);
+int rgbe_check_launch(cvvdp_handle* h);
+void launch_unpack_rgbe(const RgbeArgs& a, hipStream_t s);
+
 }  // namespace cvvdp

@@ -1,25 +1,31 @@
 """File sources, mirroring pycvvdp/video_source_file.py for the formats this build reads without ffmpeg.
 
-  load_image_as_array        video_source_file.py:36-70   8 / 16-bit image file -> [H, W, C] array
+  load_image_as_array        video_source_file.py:36-70   8 / 16-bit image file -> [H, W, C] array; Radiance .hdr -> float32 [H, W, 3]
   video_source_image_frames  video_source_file.py:549-652 an image pair, or a clip stored as numbered frames ("f_%04d.png" + fps)
   video_source_file          video_source_file.py:755-820 dispatch on the file extension (.yuv, images, .npy; compressed video
                                                           files need ffmpeg and are refused)
 
 The sources hand RAW samples to the metric (`get_raw_block`): unpacking, the display model and the colour transform happen in the
-HIP temporal kernel, not here.
+HIP temporal kernel, not here.  Radiance .hdr frames cross PCIe as the 4 bytes per pixel the file holds (R, G, B and the shared
+exponent E) and become float32 on the GPU (cvvdp_unpack_rgbe).
 """
+import ctypes
 import os
 import re
 
 import numpy as np
 import torch
 
+from . import _capi
 from .display_model import vvdp_display_photometry
 from .video_source import video_source, video_source_array
 from .video_source_yuv import video_source_yuv_file
 from .vq_metric import vq_exception
 
-IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".ppm", ".pgm", ".gif")
+IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".ppm", ".pgm", ".gif", ".hdr")
+HDR_EXT = (".hdr",)
+EXR_MESSAGE = ("OpenEXR files are not read by this build. Store the frames as Radiance .hdr files or as float32 .npy arrays "
+               "([H, W, 3] in absolute cd/m^2 for the *_linear displays)")
 VIDEO_EXT = (".mp4", ".mkv", ".mov", ".avi", ".webm", ".m4v", ".y4m")
 
 
@@ -88,10 +94,44 @@ def _palette_is_grey(im):
     return bool(pal.size == 0 or (np.all(pal[:, 0] == pal[:, 1]) and np.all(pal[:, 1] == pal[:, 2])))
 
 
+def load_rgbe(fname):
+    """Radiance .hdr file -> uint8 [H, W, 4] (R, G, B, E): the file's own samples, run-length decoding undone (cvvdp_rgbe_decode).
+    A file the reader refuses raises vq_exception with the reader's message."""
+    if not os.path.isfile(fname):
+        raise FileNotFoundError(f"File '{fname}' not found")
+    lib = _capi.lib()
+    data = np.fromfile(fname, dtype=np.uint8)
+    src = data.ctypes.data if data.size else np.zeros(1, dtype=np.uint8).ctypes.data      # (an empty file: a valid pointer, length 0)
+    w, h = ctypes.c_int32(), ctypes.c_int32()
+    rc = lib.cvvdp_rgbe_header(src, data.size, ctypes.byref(w), ctypes.byref(h), None)
+    if rc == 0:
+        # (the header probe has checked the file's length against the size it claims: the allocation is at most ~127 x the file)
+        out = np.empty((h.value, w.value, 4), dtype=np.uint8)
+        rc = lib.cvvdp_rgbe_decode(src, data.size, out.ctypes.data, out.nbytes)
+    if rc != 0:
+        raise vq_exception(f"'{fname}': {lib.cvvdp_rgbe_strerror(rc).decode()}")
+    return out
+
+
+def rgbe_to_float(rgbe):
+    """uint8 [..., 4] (R, G, B, E) -> float32 [..., 3]: mantissa * 2^(E - 136), 0 where E == 0.  Exact in float32 (the GPU's
+    cvvdp_unpack_rgbe gives the same bits)."""
+    e = rgbe[..., 3].astype(np.int32)
+    v = np.ldexp(rgbe[..., :3].astype(np.float32), (e - 136)[..., None]).astype(np.float32)
+    v[e == 0] = 0
+    return v
+
+
 def load_image_as_array(fname):
-    """8- or 16-bit image file -> uint8 / uint16 array [H, W, C] (the reference reads them with imageio, video_source_file.py)."""
+    """8- or 16-bit image file -> uint8 / uint16 array [H, W, C] (the reference reads them with imageio, video_source_file.py);
+    Radiance .hdr -> float32 [H, W, 3], the file's values as they are (no EXPOSURE= scaling, as imageio's FreeImage reader)."""
     if not os.path.isfile(fname):
         raise FileNotFoundError(f"File '{fname}' not found")                                     # video_source_file.py:37-40
+    ext = os.path.splitext(fname)[1].lower()
+    if ext == ".exr":
+        raise vq_exception(f"'{fname}': {EXR_MESSAGE}")
+    if ext in HDR_EXT:
+        return rgbe_to_float(load_rgbe(fname))
     if _png_is_16bit_colour(fname):
         return _read_png16(fname)
     from PIL import Image
@@ -112,7 +152,8 @@ class video_source_image_frames(video_source):
     as numbered frames -- both names then carry a C-style frame-number field such as "%04d", fps > 0, and the frames of
     `frame_range` (default 0, 1, 2, ...) are used up to the first number for which either file is missing.
 
-    Frames are decoded on demand, a block at a time (`get_raw_block`), and handed to the metric as 8 / 16-bit codes."""
+    Frames are decoded on demand, a block at a time (`get_raw_block`), and handed to the metric as 8 / 16-bit codes.  Radiance .hdr
+    frames are kept as their RGBE bytes, uploaded at 4 bytes per pixel and unpacked to float32 on the GPU."""
 
     device_resident = False        # frames cross PCIe block by block: the core keeps the temporal history itself
 
@@ -150,6 +191,16 @@ class video_source_image_frames(video_source):
             self.frame_range = frame_range[0:count]
         self._size = None
         self._first = None
+        kinds = [os.path.splitext(n)[1].lower() in HDR_EXT for n in (test_fname, reference_fname)]
+        if kinds[0] != kinds[1]:
+            raise vq_exception(f"Test and reference must both be Radiance .hdr files or both 8 / 16-bit images ('{test_fname}' vs '{reference_fname}')")
+        self._hdr = kinds[0]
+        self._core = None              # C handle for cvvdp_unpack_rgbe (it carries the error text; the call touches no handle state)
+
+    def __del__(self):
+        core, self._core = getattr(self, "_core", None), None
+        if core:
+            _capi.lib().cvvdp_destroy(core)
 
     _format_re = re.compile(r"%(\d)*d")
 
@@ -173,7 +224,8 @@ class video_source_image_frames(video_source):
             pair, self._first = self._first, None            # the pair read for get_video_size
             return pair
         ft, fr = self._names(frame)
-        t, r = load_image_as_array(ft), load_image_as_array(fr)
+        load = load_rgbe if self._hdr else load_image_as_array
+        t, r = load(ft), load(fr)
         if t.shape != r.shape or t.dtype != r.dtype:
             raise vq_exception(f"Test and reference images differ in size or bit depth: '{ft}' {t.shape} {t.dtype} vs '{fr}' {r.shape} {r.dtype}")
         return t, r
@@ -201,13 +253,41 @@ class video_source_image_frames(video_source):
                                    f"the first frame {self._fmt[0]} with {self._fmt[1]}")
             for side in range(2):
                 a = pair[side]
+                if self._hdr:
+                    if out[side] is None:
+                        out[side] = torch.empty((last - first, h, w, 4), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+                    out[side][k] = torch.from_numpy(a)
+                    continue
                 a = a.view(np.int16) if a.dtype == np.uint16 else a        # torch has no uint16 (video_source.py:259-263)
                 t = torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))
                 if out[side] is None:
                     out[side] = torch.empty((1, t.shape[0], last - first, h, w), dtype=t.dtype, pin_memory=torch.cuda.is_available())
                     code = 1 if t.dtype == torch.int16 else 0
                 out[side][0, :, k] = t
+        if self._hdr:
+            return self._unpack_rgbe(out[0], device), self._unpack_rgbe(out[1], device), _capi.F32
         return out[0].to(device, non_blocking=True), out[1].to(device, non_blocking=True), code
+
+    def _unpack_rgbe(self, staged, device):
+        """Pinned RGBE block [n, H, W, 4] -> float32 [1, 3, n, H, W] on `device`: the upload is 4 bytes per pixel, the 12 the metrics read
+        are written by cvvdp_unpack_rgbe on the current stream."""
+        lib = _capi.lib()
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
+        if self._core is None:
+            core = ctypes.c_void_p()
+            if lib.cvvdp_create(ctypes.byref(_capi.Params()), ctypes.byref(core)) != 0:
+                raise RuntimeError("cvvdp_create failed")
+            self._core = core
+        n, h, w, _ = staged.shape
+        with torch.cuda.device(device):
+            codes = staged.to(device, non_blocking=True)
+            rgb = torch.empty((1, 3, n, h, w), dtype=torch.float32, device=device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            rc = lib.cvvdp_unpack_rgbe(self._core, codes.data_ptr(), n, h, w, rgb.data_ptr(), rgb.stride(1), rgb.stride(2), stream)
+        _capi.check(self._core, rc, "cvvdp_unpack_rgbe")
+        return rgb              # (codes: stream-ordered, the caching allocator may reuse it once the kernel is queued)
 
     def get_test_frame(self, frame, device, colorspace="Y"):
         raise NotImplementedError("image frames are converted on the GPU by colorvideovdp_amd.cvvdp.predict_video_source")
@@ -223,6 +303,9 @@ class video_source_file(video_source):
                  full_screen_resize=None, resize_resolution=None, preload=False, ffmpeg_cc=False, verbose=False):
         ext = os.path.splitext(test_fname)[1].lower()
         ext_r = os.path.splitext(reference_fname)[1].lower()
+        for f, e in ((test_fname, ext), (reference_fname, ext_r)):
+            if e == ".exr":
+                raise vq_exception(f"'{f}': {EXR_MESSAGE}")
         if (ext in IMAGE_EXT) != (ext_r in IMAGE_EXT):
             raise vq_exception("Test is an image, but reference is a video" if ext in IMAGE_EXT else "Test is a video, but reference is an image")
         if ext in IMAGE_EXT:

@@ -303,6 +303,39 @@ int cvvdp_pixel_ssim(cvvdp_handle* h, const void* dev_test, const void* dev_ref,
 /* sizeof(cvvdp_ssim_args) as compiled. */
 int32_t cvvdp_ssim_args_size(void);
 
+/* Radiance RGBE images (.hdr), the reference's HDR image input (pycvvdp/video_source_file.py:36-70 reads them with imageio / FreeImage).
+ * Two host entries read the file's bytes; they touch neither a handle nor the GPU.  The input is untrusted: nothing is allocated, and
+ * nothing is written before the data has been shown to be long enough for the size the header claims.
+ *   cvvdp_rgbe_header  width, height and the offset of the first scanline (data_offset may be NULL).  Fails with
+ *                      CVVDP_E_RGBE_TRUNCATED when the data behind the header is shorter than height scanlines of that width can be
+ *   cvvdp_rgbe_decode  uint8 [height][width][4] (R, G, B, E) into out_rgbe, a buffer of out_bytes >= 4 * width * height bytes
+ * Scanlines are flat or new-style run-length encoded, in any mix; old-style run markers inside flat data are not interpreted, and
+ * EXPOSURE= and the other header variables are ignored (FreeImage does not apply them either).  Every failure has its own code;
+ * cvvdp_rgbe_strerror gives its text (a static string, never NULL). */
+enum {
+  CVVDP_E_RGBE_MAGIC = -101,          /* does not begin with #?RADIANCE or #?RGBE */
+  CVVDP_E_RGBE_XYZE = -102,           /* FORMAT=32-bit_rle_xyze: refused, the values are not RGB */
+  CVVDP_E_RGBE_ORIENTATION = -103,    /* a resolution line other than -Y H +X W */
+  CVVDP_E_RGBE_SIZE = -104,           /* the resolution line is missing, or a size is not a positive number */
+  CVVDP_E_RGBE_BUFFER = -105,         /* 4 * W * H exceeds out_bytes, or is not representable */
+  CVVDP_E_RGBE_TRUNCATED = -106,      /* the data ends early (in the header, or before the last scanline is complete) */
+  CVVDP_E_RGBE_RUN = -107,            /* a run crosses the end of its scanline */
+  CVVDP_E_RGBE_SCANLINE_WIDTH = -108, /* a new-style scanline header whose width is not W */
+  CVVDP_E_RGBE_ZERO_COUNT = -109      /* a run of length 0 */
+};
+int cvvdp_rgbe_header(const void* data, size_t len, int32_t* width, int32_t* height, size_t* data_offset);
+int cvvdp_rgbe_decode(const void* data, size_t len, void* out_rgbe, size_t out_bytes);
+const char* cvvdp_rgbe_strerror(int code);
+
+/* RGBE bytes -> fp32 on the device.  dev_rgbe holds n_frames frames of uint8 [H][W][4], packed back to back (4-byte aligned);
+ * dev_out receives fp32 planes: channel c of frame f starts at dev_out + c * stride_c + f * stride_f (strides in floats, each at least
+ * H * W; a contiguous [1, 3, n_frames, H, W] block for cvvdp_process_block / cvvdp_pixel_sse / cvvdp_pixel_ssim with CVVDP_F32 has
+ * stride_c = n_frames * H * W, stride_f = H * W).  Value: float(mantissa) * 2^(E - 136), 0 where E == 0 -- exact in fp32 for every
+ * input, subnormal results included.  One pass, 4 B in and 12 B out per pixel; needs no configured clip and touches no handle state
+ * (the handle carries the error text). */
+int cvvdp_unpack_rgbe(cvvdp_handle* h, const void* dev_rgbe, int32_t n_frames, int32_t H, int32_t W, float* dev_out, int64_t stride_c,
+                      int64_t stride_f, void* stream);
+
 /* Sources that deliver temporally pre-filtered channels (vid_source.is_temporally_filtered, cvvdp_metric.py:470-488):
  * frames are fp32 [B, 4, n, H, W] in colour space 'DKLd65_trans' (Y-sustained, RG, YV, Y-transient; element strides in
  * B,C,F,H,W order) and go straight into the 8 level-0 planes (test channel c -> plane 2c, reference -> 2c+1), bypassing
