@@ -12,6 +12,7 @@ import pytest
 import colorvideovdp_amd as cv
 from colorvideovdp_amd import _capi, cli, psnr_metric
 from colorvideovdp_amd.display_model import vvdp_display_photo_eotf, vvdp_display_photometry
+from pixel_reference import _forward, _pu, psnr_restated as _restated
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "psnr")      # a directory of their own: not cvvdp array cases
 ARRAY_CASES = sorted(p for p in glob.glob(os.path.join(GOLDEN, "psnr_*.npz")) if "test" in np.load(p).files)
@@ -101,79 +102,7 @@ def test_host_scalars_bit_identical_to_reference(path):
         assert s["rgb2020"].tobytes() == g["rgb2020"].tobytes()
 
 
-# ---------------------------------------------------------------- float64 restatement of the formulas
-def _pu(Y):
-    p = psnr_metric.PU.PARAMS["banding_glare"]
-    Y = np.clip(Y, 0.005, 10000.0)
-    yp = Y ** p[3]
-    return p[6] * (((p[0] + p[1] * yp) / (1 + p[2] * yp)) ** p[4] - p[5])
-
-
-def _forward(dm, V):
-    """vvdp_display_photo_eotf.forward (display_model.py:333-365) in float64; V: [B, C, F, H, W]."""
-    e = dm.EOTF
-    if e != "linear":
-        V = np.clip(V, 0.0, 1.0)
-    Yb, Yr = dm.get_black_level()
-    if e == "sRGB":
-        lin = np.where(V > 0.04045, ((V + 0.055) / 1.055) ** 2.4, V / 12.92)
-        return (dm.Y_peak - Yb) * lin + Yb + Yr
-    if e == "PQ":
-        n, m, c1, c2, c3 = 0.15930175781250000, 78.843750000000000, 0.83593750000000000, 18.851562500000000, 18.687500000000000
-        t = V ** (1 / m)
-        L = 10000 * (np.maximum(t - c1, 0) / (c2 - c3 * t)) ** (1 / n)
-        return np.clip(L * dm.exposure, 0.005, dm.Y_peak) + Yb + Yr
-    if e == "linear":
-        return np.clip(V * dm.exposure, max(0.005, Yb), dm.Y_peak) + Yr
-    if e == "HLG":
-        a = 0.17883277
-        b, c = 1 - 4 * a, 0.5 - a * math.log(4 * a)
-        s = np.where(V <= 0.5, V ** 2 / 3.0, (np.exp((V - c) / a) + b) / 12.0)
-        gamma = 1.2 if dm.Y_peak <= 1000 else 1.2 + 0.42 * math.log10(dm.Y_peak / 1000) - 0.07623 * math.log10(dm.E_ambient / 5)
-        Ys = 0.2627 * s[:, 0] + 0.6780 * s[:, 1] + 0.0593 * s[:, 2]
-        return (dm.Y_peak - Yb) * (Ys ** (gamma - 1))[:, None] * s + Yb + Yr
-    gamma = float(e)
-    return (dm.Y_peak - Yb) * np.clip(V ** gamma * dm.exposure, 0, 1) + Yb + Yr
-
-
-XYZ_to_RGB2020 = np.asarray(psnr_metric.XYZ_to_RGB2020)
-
-
-def _restated(g):
-    """{metric: dB[B]} from the fixture's samples: per frame mean over C, H, W of the squared difference in the metric's space, summed
-    over frames; pu-psnr-* take that of the UNENCODED linear values (Q7)."""
-    dm = _dm(g)
-    t, r = g["test"], g["ref"]
-    conv = {np.dtype(np.uint8): 255.0, np.dtype(np.uint16): 65535.0}
-    T, R = ((x.astype(np.float64) / conv[x.dtype]) if x.dtype in conv else x.astype(np.float64) for x in (t, r))
-    T, R = np.broadcast_arrays(T, R)
-    colour = T.shape[1] == 3
-    rgb2xyz = np.asarray(dm.rgb2xyz_list, dtype=np.float64) if colour else None
-    out = {}
-    # psnr_rgb: display-encoded as it is, or PU21 / PU21(100) on linear and PQ displays (display_model.py:206-226)
-    if dm.EOTF in ("linear", "PQ"):
-        enc = lambda V: _pu(_forward(dm, V)) / float(np.float32(g["pu_100"]))
-    else:
-        enc = lambda V: V
-    out["psnr_rgb"] = (enc(T) - enc(R)) ** 2
-    LT, LR = _forward(dm, T), _forward(dm, R)
-    if colour:
-        y = rgb2xyz[1]
-        out["pu_psnr_y"] = (np.einsum("c,bcfhw->bfhw", y, LT) - np.einsum("c,bcfhw->bfhw", y, LR))[:, None] ** 2
-        M = XYZ_to_RGB2020 @ rgb2xyz
-        out["pu_psnr_rgb2020"] = (np.einsum("dc,bcfhw->bdfhw", M, LT) - np.einsum("dc,bcfhw->bdfhw", M, LR)) ** 2
-    else:
-        out["pu_psnr_y"] = out["pu_psnr_rgb2020"] = (LT - LR) ** 2
-    N = T.shape[2]
-    res = {}
-    for k, sq in out.items():
-        mse = sq.mean(axis=(1, 3, 4)).sum(axis=1)
-        max_I = 1.0 if k == "psnr_rgb" else _pu(100.0)
-        with np.errstate(divide="ignore"):
-            res[k] = 20 * np.log10(max_I / np.sqrt(mse / N))
-    return res
-
-
+# ---------------------------------------------------------------- float64 restatement of the formulas (tests/pixel_reference.py)
 @pytest.mark.parametrize("path", ARRAY_CASES, ids=lambda p: os.path.basename(p)[5:-4])
 def test_float64_restatement_matches_fixture(path):
     g = np.load(path)

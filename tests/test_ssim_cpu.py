@@ -16,6 +16,7 @@ from colorvideovdp_amd import _capi, cli
 from colorvideovdp_amd.display_model import vvdp_display_photo_eotf, vvdp_display_photometry
 from colorvideovdp_amd.psnr_metric import PU
 from colorvideovdp_amd.ssim_metric import ssim_scalars
+from pixel_reference import _filter, ssim_restated as _restated  # noqa: F401
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "ssim")      # a directory of their own: not cvvdp array cases
 ALL_CASES = sorted(glob.glob(os.path.join(GOLDEN, "ssim_*.npz")))
@@ -127,59 +128,7 @@ def test_error_cases_raise_vq_exception(monkeypatch):
         m.predict_video_source(_Frames((1, 3, 2, 16, 1)))
 
 
-# ---------------------------------------------------------------- float64 restatement of the formula
-def _pu(Y):
-    p = PU.PARAMS["banding_glare"]
-    Y = np.clip(Y, 0.005, 10000.0)
-    yp = Y ** p[3]
-    return p[6] * (((p[0] + p[1] * yp) / (1 + p[2] * yp)) ** p[4] - p[5])
-
-
-def _forward(dm, V):
-    """vvdp_display_photo_eotf.forward (display_model.py:333-365) in float64 for the two displays that take the PU21 route."""
-    Yb, Yr = dm.get_black_level()
-    if dm.EOTF == "PQ":
-        V = np.clip(V, 0.0, 1.0)
-        n, m, c1, c2, c3 = 0.15930175781250000, 78.843750000000000, 0.83593750000000000, 18.851562500000000, 18.687500000000000
-        t = V ** (1 / m)
-        L = 10000 * (np.maximum(t - c1, 0) / (c2 - c3 * t)) ** (1 / n)
-        return np.clip(L * dm.exposure, 0.005, dm.Y_peak) + Yb + Yr
-    assert dm.EOTF == "linear"
-    return np.clip(V * dm.exposure, max(0.005, Yb), dm.Y_peak) + Yr
-
-
-def _filter(a, win, axis):
-    """'valid' correlation with the window along one axis; an axis shorter than the window is left alone (ssim.py:44-52)."""
-    n = a.shape[axis]
-    if n < len(win):
-        return a
-    out = 0.0
-    for k, wk in enumerate(win):
-        out = out + wk * np.take(a, range(k, k + n - len(win) + 1), axis=axis)
-    return out
-
-
-def _restated(g):
-    dm = _dm(g)
-    conv = {np.dtype(np.uint8): 255.0, np.dtype(np.uint16): 65535.0}
-    T, R = ((x.astype(np.float64) / conv[x.dtype]) if x.dtype in conv else x.astype(np.float64) for x in (g["test"], g["ref"]))
-    if dm.EOTF in ("linear", "PQ"):       # display_model.py:208-226
-        pu100 = float(np.float32(_pu(100.0)))
-        T, R = (_pu(_forward(dm, V)) / pu100 for V in (T, R))
-    win = g["win"].astype(np.float64)
-    l = g["luma"].astype(np.float64)
-    C1, C2 = float(g["C1"]), float(g["C2"])
-    total = 0.0
-    for f in range(T.shape[2]):
-        X, Y = (l[0] * V[:, 0, f] + l[1] * V[:, 1, f] + l[2] * V[:, 2, f] for V in (T, R))            # [B, H, W]
-        blur = lambda a: _filter(_filter(a, win, 1), win, 2)
-        mu1, mu2 = blur(X), blur(Y)
-        s1, s2, s12 = blur(X * X) - mu1 * mu1, blur(Y * Y) - mu2 * mu2, blur(X * Y) - mu1 * mu2
-        m = ((2 * mu1 * mu2 + C1) / (mu1 * mu1 + mu2 * mu2 + C1)) * ((2 * s12 + C2) / (s1 + s2 + C2))
-        total += m.mean()                                                                                # over the map AND the batch (Q8)
-    return total / T.shape[2]
-
-
+# ---------------------------------------------------------------- float64 restatement of the formula (tests/pixel_reference.py)
 @pytest.mark.parametrize("path", ARRAY_CASES, ids=lambda p: os.path.basename(p)[5:-4])
 def test_float64_restatement_matches_fixture(path):
     g = np.load(path)
