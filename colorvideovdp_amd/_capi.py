@@ -98,6 +98,17 @@ class SsimArgs(C.Structure):
     ]
 
 
+MSSSIM_LEVELS = 5   # CVVDP_MSSSIM_LEVELS
+
+
+class MsssimArgs(C.Structure):
+    _fields_ = [
+        ("ssim", SsimArgs),
+        ("weights", C.c_float * MSSSIM_LEVELS),
+        ("reserved", C.c_int32),
+    ]
+
+
 # CVVDP_E_RGBE_*: what cvvdp_rgbe_header / cvvdp_rgbe_decode answer to a file they do not read
 RGBE_E_MAGIC, RGBE_E_XYZE, RGBE_E_ORIENTATION, RGBE_E_SIZE, RGBE_E_BUFFER, RGBE_E_TRUNCATED, RGBE_E_RUN, RGBE_E_SCANLINE_WIDTH, RGBE_E_ZERO_COUNT = \
     range(-101, -110, -1)
@@ -133,6 +144,11 @@ SYMBOLS = {
     "cvvdp_pixel_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(YuvFormat),
                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SsimArgs), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_msssim_args_size": (C.c_int32, []),
+    "cvvdp_pixel_msssim_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cvvdp_pixel_msssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(YuvFormat),
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MsssimArgs), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_rgbe_header": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
     "cvvdp_rgbe_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "cvvdp_rgbe_strerror": (C.c_char_p, [C.c_int]),
@@ -190,6 +206,8 @@ def lib():
             raise ImportError(f"struct layout mismatch: cvvdp_psnr_args is {l.cvvdp_psnr_args_size()} bytes in the library, {C.sizeof(PsnrArgs)} in the binding")
         if l.cvvdp_ssim_args_size() != C.sizeof(SsimArgs):
             raise ImportError(f"struct layout mismatch: cvvdp_ssim_args is {l.cvvdp_ssim_args_size()} bytes in the library, {C.sizeof(SsimArgs)} in the binding")
+        if l.cvvdp_msssim_args_size() != C.sizeof(MsssimArgs):
+            raise ImportError(f"struct layout mismatch: cvvdp_msssim_args is {l.cvvdp_msssim_args_size()} bytes in the library, {C.sizeof(MsssimArgs)} in the binding")
         # The band kernels' hand-issued loads were checked against the register allocation of the compiler the library was built with
         # (cvvdp_build_info; bench.py prints it in config.library_build).  The HIP runtime in the process is whatever torch's wheel
         # bundles (here 7.0 under a 7.2 toolchain: a minor-version gap is the normal state and says nothing), so only another MAJOR

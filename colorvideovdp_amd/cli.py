@@ -1,8 +1,8 @@
 """Command line of the MI355X build: `python -m colorvideovdp_amd` / `cvvdp` (console entry in pyproject.toml).
 
 Mirrors the reference's command line (pycvvdp/run_cvvdp.py:83-118 arguments, :120-371 run_on_args) for the path this build
-implements: the `cvvdp` metric, the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020` and the SSIM metric `ssim-metric`
-(`-m cvvdp psnr-rgb ssim-metric ...`, one output line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit; Radiance .hdr for HDR images, e.g. `-d standard_hdr_linear`), planar .yuv clips (the
+implements: the `cvvdp` metric, the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020`, the SSIM metric `ssim-metric` and the MS-SSIM metric
+`ms-ssim-metric` (`-m cvvdp psnr-rgb ssim-metric ms-ssim-metric ...`, one output line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit; Radiance .hdr for HDR images, e.g. `-d standard_hdr_linear`), planar .yuv clips (the
 file name carries size, frame rate, bit depth and chroma format, video_source_yuv.py:8-62) and .npy arrays.  Same options,
 same output lines (`cvvdp=9.1234 [JOD]`, or only the number with --quiet), same side outputs (--result CSV, --features
 JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpeg and the build is GPU-only:
@@ -33,6 +33,7 @@ from . import heatmap_writers
 from .cvvdp_metric import cvvdp
 from . import psnr_metric  # noqa: F401  (registers psnr_rgb, pu_psnr_y, pu_psnr_rgb2020)
 from . import ssim_metric  # noqa: F401  (registers ssim_metric)
+from . import ms_ssim_metric  # noqa: F401  (registers ms_ssim_metric)
 from .display_model import vvdp_display_geometry, vvdp_display_photometry
 from .video_source_file import IMAGE_EXT, VIDEO_EXT, load_image_as_array, video_source_file
 from .vq_metric import vq_exception, vq_metric_dict
@@ -67,7 +68,7 @@ _OPTIONS = (
     (("--count-frames",), dict(action="store_true", default=False, help="accepted for compatibility (frame counts of .yuv / .npy inputs are exact)")),
     (("-f", "--full-screen-resize"), dict(choices=["bilinear", "bicubic", "nearest", "area"], default=None,
                                           help="resize test and reference to the display's resolution (.yuv clips; on the GPU, torch.nn.functional.interpolate semantics)")),
-    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, psnr-rgb, pu-psnr-y, pu-psnr-rgb2020, ssim-metric")),
+    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, psnr-rgb, pu-psnr-y, pu-psnr-rgb2020, ssim-metric, ms-ssim-metric")),
     (("--temp-padding",), dict(choices=["replicate", "symmetric", "valid"], default="symmetric", help="padding before the first frame ('valid': " + _NA + ")")),
     (("--pix-per-deg",), dict(type=float, default=None, help="override the display geometry")),
     (("--fps",), dict(type=float, default=None, help="frame rate: needed for .npy clips and numbered image frames (name_%%04d.png, name_%%04d.hdr), overrides a .yuv file name")),

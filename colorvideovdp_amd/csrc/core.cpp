@@ -779,7 +779,7 @@ int cvvdp_unpack_yuv_resized(cvvdp_handle* h, const void* codes, const cvvdp_yuv
 
 }  // extern "C"
 
-// cvvdp_pixel_sse (psnr.hip) and cvvdp_pixel_ssim (ssim.hip) up to the launch: argument checks and the kernel arguments.  The entry
+// cvvdp_pixel_sse (psnr.hip), cvvdp_pixel_ssim (ssim.hip) and cvvdp_pixel_msssim (msssim.hip) up to the launch: argument checks and the kernel arguments.  The entry
 // points themselves live next to their kernels, so that this file references no symbol of them.  `what` names the entry in messages;
 // n_tiles is its number of double partials per (frame, batch).
 static int pixel_prepare(const char* what, int n_tiles, cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5],
@@ -859,6 +859,58 @@ int cvvdp::ssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t d
   return CVVDP_OK;
 }
 int cvvdp::ssim_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_ssim"); }
+// cvvdp_pixel_msssim (msssim.hip): the checks of cvvdp_pixel_ssim, the size limit of ms_ssim() (ssim.py:212-215), then the five levels
+// and where they live in the caller's scratch (msssim_layout, kernels.h)
+int cvvdp::msssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
+                          const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_msssim_args* args,
+                          double* msssim, double* levels, void* scratch, size_t scratch_bytes, MsssimArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!args || !levels) return fail(h, CVVDP_E_ARG, "pixel_msssim: null argument");
+  if (args->ssim.target != CVVDP_PSNR_AS_IS && args->ssim.target != CVVDP_PSNR_PU21)
+    return fail(h, CVVDP_E_ARG, "pixel_msssim: target %d is neither CVVDP_PSNR_AS_IS nor CVVDP_PSNR_PU21", args->ssim.target);
+  if (C != 3) return fail(h, CVVDP_E_ARG, "pixel_msssim: bad geometry C=%d, luma is taken from three channels", C);
+  cvvdp_psnr_args pa{};
+  pa.target = args->ssim.target;
+  for (int i = 0; i < 7; ++i) pa.pu_p[i] = args->ssim.pu_p[i];
+  pa.pu_L_min = args->ssim.pu_L_min; pa.pu_L_max = args->ssim.pu_L_max; pa.pu_norm = args->ssim.pu_norm;
+  a = MsssimArgs{};
+  // (the scratch is checked below against the layout of all levels)
+  if (int rc = pixel_prepare("pixel_msssim", 0, h, t, r, dtype, st, sr, yuv, B, C, n_frames, H, W, &pa, msssim, scratch, scratch_bytes, a.s.p))
+    return rc;
+  if (H <= kMsMinSide || W <= kMsMinSide)
+    return fail(h, CVVDP_E_ARG, "pixel_msssim: frames of %dx%d: the smaller side must be larger than %d (four 2x downsamplings of an 11-tap window)",
+                W, H, kMsMinSide);
+  const MsssimLayout l = msssim_layout(B, n_frames, H, W);
+  if (scratch_bytes < l.total) return fail(h, CVVDP_E_ARG, "pixel_msssim: scratch too small");
+  if (reinterpret_cast<uintptr_t>(scratch) % 8 != 0) return fail(h, CVVDP_E_ARG, "pixel_msssim: scratch is not 8-byte aligned");
+  SsimArgs& s = a.s;
+  for (int i = 0; i < kSsimWin; ++i) s.win[i] = args->ssim.win[i];
+  s.C1 = args->ssim.C1; s.C2 = args->ssim.C2;
+  for (int i = 0; i < 3; ++i) s.luma[i] = args->ssim.luma[i];
+  s.Hm = ssim_map_size(H); s.Wm = ssim_map_size(W);
+  s.fv = 1; s.fh = 1;
+  s.tiles_x = ssim_tiles_x(W); s.tiles_y = ssim_tiles_y(H);
+  s.p.n_tiles = l.tiles[0];
+  char* base = static_cast<char*>(scratch);
+  s.p.partial = reinterpret_cast<double*>(base + l.part_ssim[0]);
+  for (int k = 0; k < kMsLevels; ++k) {
+    MsssimLevel& L = a.lv[k];
+    L.H = l.H[k]; L.W = l.W[k]; L.Hm = ssim_map_size(L.H); L.Wm = ssim_map_size(L.W);
+    L.tiles_x = ssim_tiles_x(L.W); L.n_tiles = l.tiles[k];
+    const bool last = k == kMsLevels - 1;
+    L.part_cs = last ? nullptr : reinterpret_cast<double*>(base + l.part_cs[k]);
+    L.part_ssim = (k == 0 || last) ? reinterpret_cast<double*>(base + l.part_ssim[k]) : nullptr;
+    for (int side = 0; side < 2; ++side) {
+      L.src[side] = k == 0 ? nullptr : reinterpret_cast<const float*>(base + l.plane[k][side]);
+      L.pool[side] = last ? nullptr : reinterpret_cast<float*>(base + l.plane[k + 1][side]);
+    }
+    L.Hn = last ? 0 : l.H[k + 1]; L.Wn = last ? 0 : l.W[k + 1];
+    a.weights[k] = (double)args->weights[k];
+  }
+  a.msssim = msssim; a.levels = levels;
+  return CVVDP_OK;
+}
+int cvvdp::msssim_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_msssim"); }
 // cvvdp_unpack_rgbe (rgbe.hip) up to the launch
 int cvvdp::rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int32_t H, int32_t W, float* out, int64_t stride_c,
                         int64_t stride_f, RgbeArgs& a) {

@@ -354,6 +354,60 @@ int ssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, c
 int ssim_check_launch(cvvdp_handle* h);
 void launch_pixel_ssim(const SsimArgs& a, double* ssim, double* acc, hipStream_t s);
 
+// ---------------------------------------------------------------- MS-SSIM metric (msssim.hip)
+// Five levels of the SSIM walk above (same tiling, both dimensions always filtered: min(H, W) > kMsMinSide keeps the last level at
+// 11 samples or more).  Level 0 reads the frames, levels 1..4 read fp32 luma planes; levels 0..3 write the next level's planes.
+constexpr int kMsLevels = CVVDP_MSSSIM_LEVELS;
+constexpr int kMsMinSide = (kSsimWin - 1) * 16;     // ssim.py:212-215: the smaller side must be larger than this
+struct MsssimLevel {
+  const float* src[2];      // levels 1..4: luma planes [frame][batch][H][W] of test and ref; level 0: null (the frames of SsimArgs::p)
+  float* pool[2];           // levels 0..3: the next level's planes [frame][batch][Hn][Wn]; level 4: null
+  double* part_cs;          // [frame][batch][tile] sums of the cs map (levels 0..3), or null
+  double* part_ssim;        // [frame][batch][tile] sums of the SSIM map (levels 0 and 4), or null
+  int32_t H, W, Hm, Wm;     // size of the level and of its maps
+  int32_t tiles_x, n_tiles;
+  int32_t Hn, Wn;           // size of the next level: (n + n % 2) / 2
+};
+struct MsssimArgs {
+  SsimArgs s;               // s.p.H / W / n_tiles, s.Hm / Wm / tiles_x / tiles_y describe level 0
+  MsssimLevel lv[kMsLevels];
+  double weights[kMsLevels];
+  double* msssim;           // [frame][batch]
+  double* levels;           // [frame][batch][level]
+};
+static_assert(sizeof(SsimArgs) + sizeof(MsssimLevel) <= 4096, "kernel arguments of the MS-SSIM kernels");
+inline int msssim_next_size(int n) { return (n + (n & 1)) / 2; }     // avg_pool2d(kernel_size=2, padding=n % 2), ssim.py:232-234
+// The caller's scratch (include/cvvdp_hip.h): byte offsets.  items = B * n_frames.
+struct MsssimLayout {
+  int32_t H[kMsLevels], W[kMsLevels], tiles[kMsLevels];
+  size_t part_cs[kMsLevels], part_ssim[kMsLevels];    // part_cs[4] and part_ssim[1..3] are unused (= total)
+  size_t plane[kMsLevels][2];                         // plane[0] unused
+  size_t total;
+};
+inline MsssimLayout msssim_layout(int B, int n_frames, int H, int W) {
+  MsssimLayout l{};
+  const size_t items = (size_t)B * n_frames;
+  l.H[0] = H; l.W[0] = W;
+  for (int k = 1; k < kMsLevels; ++k) { l.H[k] = msssim_next_size(l.H[k - 1]); l.W[k] = msssim_next_size(l.W[k - 1]); }
+  size_t off = 0;
+  for (int k = 0; k < kMsLevels; ++k) {
+    l.tiles[k] = ssim_tiles(l.H[k], l.W[k]);
+    const size_t bytes = items * l.tiles[k] * sizeof(double);
+    l.part_cs[k] = off; if (k < kMsLevels - 1) off += bytes;
+    l.part_ssim[k] = off; if (k == 0 || k == kMsLevels - 1) off += bytes;
+  }
+  for (int k = 1; k < kMsLevels; ++k)
+    for (int side = 0; side < 2; ++side) { l.plane[k][side] = off; off += items * l.H[k] * l.W[k] * sizeof(float); }
+  l.total = off;
+  return l;
+}
+// core.cpp: argument checks and kernel arguments of cvvdp_pixel_msssim; the error of a launch
+int msssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
+                   const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_msssim_args* args,
+                   double* msssim, double* levels, void* scratch, size_t scratch_bytes, MsssimArgs& a);
+int msssim_check_launch(cvvdp_handle* h);
+void launch_pixel_msssim(const MsssimArgs& a, double* acc, hipStream_t s);
+
 // ---------------------------------------------------------------- Radiance RGBE frames (rgbe.hip)
 // n_frames frames of uint8 [H][W][4] (R, G, B, E), packed back to back -> fp32 planes: channel c of frame f at dst + c * sc + f * sf.
 constexpr int kRgbeThreads = 256;

@@ -191,21 +191,26 @@ class _psnr_base(vq_metric):
             sr[0] = 0
         return (ctypes.c_int64 * 5)(*st), (ctypes.c_int64 * 5)(*sr)
 
-    def _block_frames(self, bytes_per_frame, N, resident):
+    def _block_frames(self, bytes_per_frame, N, resident, scratch_per_frame=0):
         """Frames per call: a device-resident clip is scored in one call; frames that have to be copied or unpacked first come in blocks
-        sized to a quarter of the free device memory."""
+        sized to a quarter of the free device memory.  A metric whose kernels need `scratch_per_frame` bytes of device scratch per frame
+        of a call (MS-SSIM: the pooled planes) has every clip, a resident one too, cut so that a call's scratch stays below a quarter
+        of the free memory as well."""
         if self.block_frames is not None:
             return max(1, int(self.block_frames))
-        if resident:
+        if resident and scratch_per_frame <= 0:
             return N
         free, _ = torch.cuda.mem_get_info(self.device)
-        return int(max(1, min(N, 4096, (free // 4) // max(1, bytes_per_frame))))
+        nb = N if resident else min(N, 4096, (free // 4) // max(1, bytes_per_frame))
+        if scratch_per_frame > 0:
+            nb = min(nb, (free // 4) // scratch_per_frame)
+        return int(max(1, nb))
 
-    def _blocks(self, vs, H, W, N, B, is_yuv, raw, args):
+    def _blocks(self, vs, H, W, N, B, is_yuv, raw, args, scratch_per_frame=0):
         """(test, ref, dtype code, Y'CbCr format or None, channels, frames) per block of frames."""
         if is_yuv:
             resize = bool(getattr(vs, "needs_resize", lambda: False)())
-            nb = self._block_frames((12 if resize else 4) * 3 * H * W, N, False)
+            nb = self._block_frames((12 if resize else 4) * 3 * H * W, N, False, scratch_per_frame)
             for a in range(0, N, nb):
                 b = min(N, a + nb)
                 if resize:
@@ -217,7 +222,7 @@ class _psnr_base(vq_metric):
         elif isinstance(vs, video_source_array):
             t, r, code = vs.raw_arrays()
             resident = t.device == self.device and r.device == self.device
-            nb = self._block_frames(2 * B * t.shape[1] * H * W * t.element_size(), N, resident)
+            nb = self._block_frames(2 * B * t.shape[1] * H * W * t.element_size(), N, resident, scratch_per_frame)
             for a in range(0, N, nb):
                 b = min(N, a + nb)
                 tb = t[:, :, a:b] if t.device == self.device else t[:, :, a:b].to(self.device)
@@ -225,7 +230,7 @@ class _psnr_base(vq_metric):
                 yield tb, rb, code, None, t.shape[1], b - a
         elif raw:
             resident = bool(getattr(vs, "device_resident", False))
-            nb = self._block_frames(2 * B * 3 * H * W * 4, N, resident)
+            nb = self._block_frames(2 * B * 3 * H * W * 4, N, resident, scratch_per_frame)
             for a in range(0, N, nb):
                 b = min(N, a + nb)
                 t, r, code = vs.get_raw_block(a, b, self.device)
@@ -233,7 +238,7 @@ class _psnr_base(vq_metric):
         else:
             # generic source: frames arrive one by one, already in the metric's colour space (psnr_metric.py:36-43, :82-86)
             args.target = _capi.PSNR_AS_IS
-            nb = self._block_frames(2 * B * 3 * H * W * 4, N, False)
+            nb = self._block_frames(2 * B * 3 * H * W * 4, N, False, scratch_per_frame)
             for a in range(0, N, nb):
                 b = min(N, a + nb)
                 ts, rs = [], []

@@ -303,6 +303,43 @@ int cvvdp_pixel_ssim(cvvdp_handle* h, const void* dev_test, const void* dev_ref,
 /* sizeof(cvvdp_ssim_args) as compiled. */
 int32_t cvvdp_ssim_args_size(void);
 
+/* MS-SSIM metric (ms_ssim() of pycvvdp/third_party/ssim.py:164-243 on the lumas cvvdp_pixel_ssim takes; the reference package has the
+ * function but no metric class around it).  Five levels.  At each level the SSIM walk above gives the mean of the SSIM map and the
+ * mean of the contrast-structure map cs (ssim.py:97-101); between levels both lumas are averaged 2 x 2 with
+ * avg_pool2d(kernel_size=2, padding=[H % 2, W % 2]) (ssim.py:232-234): the next size is (n + n % 2) / 2, pooled sample i covers inputs
+ * 2i - n % 2 and 2i - n % 2 + 1, a sample outside the level counts as 0 and the divisor is always 4.  The in-range samples are added top
+ * row first, left to right, in fp32, and the sum is multiplied by 0.25.  Levels 0..3 contribute relu(mean cs), level 4 relu(mean ssim);
+ * the result is the product of value ^ weight over the levels (ssim.py:236-238), taken in double: a level mean <= 0 gives exactly 0.
+ * The arguments are those of cvvdp_pixel_ssim, with
+ *   H, W              min(H, W) > 160 (ssim.py:212-215); smaller frames are refused with CVVDP_E_ARG
+ *   dev_msssim        double [n_frames][B]: MS-SSIM of frame f, batch item b
+ *   dev_levels        double [n_frames][B][5]: the level means before relu, cs for levels 0..3 and SSIM for level 4
+ *   dev_acc           double [1] or NULL: in frame order, acc += (sum over b of msssim[f][b]) / B (size_average=True ends in a plain
+ *                     mean over the batch, ssim.py:240-241)
+ *   dev_scratch       cvvdp_pixel_msssim_scratch_bytes(B, n_frames, H, W) bytes, 8-byte aligned.  Layout, with items = n_frames * B in
+ *                     [frame][batch] order, T_k = tiles of level k (ceil((H_k - 10) / 64) * ceil((W_k - 10) / 246)), sizes H_k x W_k:
+ *                       double cs0[items][T_0], ssim0[items][T_0]      per-tile sums of both maps of level 0
+ *                       double cs1[items][T_1], cs2[items][T_2], cs3[items][T_3], ssim4[items][T_4]
+ *                       float  test1[items][H_1][W_1], ref1[items][H_1][W_1], test2 ..., ref2 ..., test3, ref3, test4, ref4
+ *                     Every element is written by every call, exactly once.
+ * Level 0 is one fused pass over the frames (each sample is read once per tile; no full-size luma plane exists); it writes the pooled
+ * planes of level 1 itself, and so does each further level for the next one: pooled sample (i, j) is written by the workgroup whose
+ * tile holds its first in-range input sample.  Sums as in cvvdp_pixel_ssim: fp32 down a thread's column segment, then double in an
+ * order that depends only on H and W (no atomics). */
+#define CVVDP_MSSSIM_LEVELS 5
+typedef struct cvvdp_msssim_args {
+  cvvdp_ssim_args ssim;                  /* target, window, C1, C2, luma weights, PU21 constants */
+  float weights[CVVDP_MSSSIM_LEVELS];    /* fp32 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 (ssim.py:217-219) */
+  int32_t reserved;
+} cvvdp_msssim_args;
+size_t cvvdp_pixel_msssim_scratch_bytes(int32_t B, int32_t n_frames, int32_t H, int32_t W);
+int cvvdp_pixel_msssim(cvvdp_handle* h, const void* dev_test, const void* dev_ref, int32_t dtype, const int64_t strides_test[5],
+                       const int64_t strides_ref[5], const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W,
+                       const cvvdp_msssim_args* args, double* dev_msssim, double* dev_levels, double* dev_acc, void* dev_scratch,
+                       size_t scratch_bytes, void* stream);
+/* sizeof(cvvdp_msssim_args) as compiled. */
+int32_t cvvdp_msssim_args_size(void);
+
 /* Radiance RGBE images (.hdr), the reference's HDR image input (pycvvdp/video_source_file.py:36-70 reads them with imageio / FreeImage).
  * Two host entries read the file's bytes; they touch neither a handle nor the GPU.  The input is untrusted: nothing is allocated, and
  * nothing is written before the data has been shown to be long enough for the size the header claims.
