@@ -97,7 +97,8 @@ def test_block_size_invariance(name, block):
 
 
 def test_intermediates_against_oracle():
-    """Ring (DKL), temporal channels, Gaussian pyramid and per-pixel D of every band vs the CPU oracle."""
+    """Ring (DKL), temporal channels, Gaussian pyramid and per-pixel D of every band vs the CPU oracle.
+    (The first stage alone, every frame, route and sample format against float64: test_fir_probe_gpu.py.)"""
     from colorvideovdp_amd import _capi
     from oracle import cvvdp_oracle as orc
     g = load_golden("vid_u8_72x128x12_60_fhd")
