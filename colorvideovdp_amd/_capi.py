@@ -134,6 +134,8 @@ SYMBOLS = {
                                           C.c_int32, C.c_int32, C.c_void_p]),
     "cvvdp_unpack_yuv_resized": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cvvdp_fir_resampled_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvvdp_psnr_args_size": (C.c_int32, []),
     "cvvdp_pixel_sse_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "cvvdp_pixel_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(YuvFormat),

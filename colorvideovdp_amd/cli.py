@@ -10,9 +10,12 @@ JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpe
   * the heat map of a VIDEO is streamed block by block: into `<base>_heatmap.mp4` through an ffmpeg pipe (the reference's
     file and codec settings) where an `ffmpeg` executable exists, otherwise into a numbered PNG sequence
     `<base>_heatmap_%05d.png` (`ffmpeg -i <base>_heatmap_%05d.png <base>_heatmap.mp4` converts it); an image gives `<base>_heatmap.png`;
-  * --device must be a cuda device; --temp-padding 'valid', --temp-resample, --dump-channels and two of the metrics the reference does not
+  * --device must be a cuda device; --temp-padding 'valid', --dump-channels and two of the metrics the reference does not
     register by default (dm-preview, the cvvdp-ml heads) are not available; --full-screen-resize works for .yuv clips (as in the
-    reference it is not implemented for images).
+    reference it is not implemented for images);
+  * --temp-resample [X] scores .yuv clips whose file names carry different frame rates (a 30 fps encode against its 60 fps source) at
+    min(lcm of the two rates, X or 166) frames per second like the reference (video_source_file.py:482-543), for the cvvdp metric,
+    without --full-screen-resize; as in the reference --fps is ignored with it.
 Clips stored as numbered image frames work as in the reference: `-t t_%04d.png -r r_%04d.png --fps 30 [--frames 10:2:50]`.
 Radiance .hdr frames work the same way (`-t t_%04d.hdr -r r_%04d.hdr --fps 24`); test and reference must then both be .hdr.  OpenEXR
 files (.exr) are not read: store such frames as .hdr or as float32 .npy arrays.
@@ -36,6 +39,7 @@ from . import ssim_metric  # noqa: F401  (registers ssim_metric)
 from . import ms_ssim_metric  # noqa: F401  (registers ms_ssim_metric)
 from .display_model import vvdp_display_geometry, vvdp_display_photometry
 from .video_source_file import IMAGE_EXT, VIDEO_EXT, load_image_as_array, video_source_file
+from .video_source_temp_resample import video_source_temp_resample_file
 from .vq_metric import vq_exception, vq_metric_dict
 
 
@@ -78,7 +82,8 @@ _OPTIONS = (
     (("-v", "--verbose"), dict(action="store_true", default=False, help="more log output")),
     (("--debug",), dict(action="store_true", default=False, help="stack traces for errors")),
     (("--ffmpeg-cc",), dict(action="store_true", default=False, help="accepted for compatibility, no effect")),
-    (("--temp-resample",), dict(type=float, nargs="?", default=-1, const=0, help=_NA)),
+    (("--temp-resample",), dict(type=float, nargs="?", default=-1, const=0,
+                                help="score .yuv clips of different frame rates at a common rate (frames repeated); optional value = the highest such rate (default 166)")),
     (("-i", "--interactive"), dict(action="store_true", default=False, help="one command line per line of standard input")),
     (("--dump-channels",), dict(nargs="+", choices=["temporal", "lpyr", "difference"], default=None, help=_NA)),
 )
@@ -94,9 +99,13 @@ def parse_args(arg_list=None):
 
 
 def load_source(test_file, ref_file, display_photometry, config_paths, nframes=-1, fps=None, frame_range=None, full_screen_resize=None,
-                resize_resolution=None):
+                resize_resolution=None, temp_resample=-1):
     """The reference's video_source_file dispatch (run_cvvdp.py:296-318) for the formats available here; returns the source
-    that does the work."""
+    that does the work.  temp_resample >= 0 (--temp-resample [X]; 0: the default cap): video_source_temp_resample_file (run_cvvdp.py:302-312)."""
+    if temp_resample >= 0:
+        kw = dict(max_fps=temp_resample) if temp_resample > 0 else {}
+        return video_source_temp_resample_file(test_file, ref_file, display_photometry=display_photometry, config_paths=config_paths, frames=nframes,
+                                               full_screen_resize=full_screen_resize, resize_resolution=resize_resolution, **kw)
     return video_source_file(test_file, ref_file, display_photometry=display_photometry, config_paths=config_paths, frames=nframes, fps=fps,
                              frame_range=frame_range, full_screen_resize=full_screen_resize, resize_resolution=resize_resolution).vs
 
@@ -136,7 +145,14 @@ def run_on_args(args):
         if opt is not None:
             raise vq_exception(f"{what} is not available in the MI355X build")
     if args.temp_resample >= 0:
-        raise vq_exception("--temp-resample is not available in the MI355X build")
+        # refused before any file or device is touched: what the resampling source does not read
+        for f in (args.test or []) + (args.ref or []):
+            if os.path.splitext(f)[1].lower() != ".yuv":
+                raise vq_exception(f"--temp-resample reads planar .yuv clips only ('{f}'); decode compressed video to .yuv first")
+        if args.full_screen_resize is not None:
+            raise vq_exception("--full-screen-resize is not available together with --temp-resample")
+        if args.fps is not None:
+            logging.warning("--fps is ignored with --temp-resample: the frame rates come from the .yuv file names")
     if args.temp_padding == "valid":
         raise vq_exception("--temp-padding valid is not available in the MI355X build (replicate or symmetric)")
     device = args.device.lower()
@@ -197,7 +213,8 @@ def run_on_args(args):
             logging.info(f"Predicting the quality of '{test_file}' compared to '{ref_file}'")
             for mm in metrics:
                 vs = load_source(test_file, ref_file, display_photometry, args.config_paths, nframes=args.nframes, fps=args.fps, frame_range=frame_range,
-                                 full_screen_resize=args.full_screen_resize, resize_resolution=display_geometry.resolution)
+                                 full_screen_resize=args.full_screen_resize, resize_resolution=display_geometry.resolution,
+                                 temp_resample=args.temp_resample)
                 base = os.path.splitext(os.path.basename(test_file))[0]
                 mm.set_base_fname(os.path.join(out_dir, base))
                 is_video = vs.get_video_size()[2] > 1

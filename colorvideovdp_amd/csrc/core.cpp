@@ -930,6 +930,33 @@ int cvvdp::rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int
 }
 int cvvdp::rgbe_check_launch(cvvdp_handle* h) { return check_launch(h, "unpack_rgbe"); }
 int cvvdp::psnr_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_sse"); }
+// cvvdp_fir_resampled_yuv (temporal_resample.hip) up to the launch: argument checks and the kernel arguments (the entry point lives next to
+// its kernels, like the pixel metrics')
+int cvvdp::fir_resampled_prepare(cvvdp_handle* h, const void* t, const void* r, const cvvdp_yuv_format* fmt, int32_t H, int32_t W,
+                                 const int32_t n_src[2], int32_t depth, const float* w_t, const float* w_r, const int32_t* e_t,
+                                 const int32_t* e_r, int32_t n_out, float* out_t, float* out_r, ResampleArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!t || !r || !n_src || !w_t || !w_r || !e_t || !e_r || !out_t || !out_r) return fail(h, CVVDP_E_ARG, "fir_resampled: null argument");
+  if (H < 1 || W < 1 || (int64_t)H * W > 0x7fff0000) return fail(h, CVVDP_E_ARG, "fir_resampled: bad frame size %dx%d", W, H);
+  if (n_out < 1 || n_out > 65535 || n_src[0] < 1 || n_src[1] < 1) return fail(h, CVVDP_E_ARG, "fir_resampled: bad frame counts");
+  if (depth < 1 || depth > CVVDP_MAX_WINDOW) return fail(h, CVVDP_E_ARG, "fir_resampled: window depth %d out of range", depth);
+  a = ResampleArgs{};
+  if (int rc = fill_yuv(h, fmt, W, H, a.f.yuv)) return rc;
+  a.f.src[0] = t; a.f.src[1] = r;
+  a.f.sf[0] = fmt->frame_stride_test; a.f.sf[1] = fmt->frame_stride_ref;
+  for (int k = 0; k < 2; ++k) { a.f.sh[k] = W; a.f.sw[k] = 1; }
+  a.f.dtype = fmt->bit_depth == 8 ? CVVDP_YUV8 : CVVDP_YUV16;
+  fill_display(h, a.f.dm);
+  a.f.dm.channels = 3;         // (no clip needs to be configured)
+  a.f.W = W; a.f.P = H * W; a.f.batch = 1;
+  a.n_src[0] = n_src[0]; a.n_src[1] = n_src[1];
+  a.n_out = n_out; a.depth = depth;
+  a.weights[0] = w_t; a.weights[1] = w_r;
+  a.emit[0] = e_t; a.emit[1] = e_r;
+  a.out[0] = out_t; a.out[1] = out_r;
+  return CVVDP_OK;
+}
+int cvvdp::fir_resampled_check_launch(cvvdp_handle* h) { return check_launch(h, "fir resampled"); }
 
 extern "C" {
 

@@ -132,6 +132,24 @@ inline int fir_kernel_len(int fl) {
   return fl;
 }
 
+// Temporal FIR over frame-repeated (resampled) clips with host-folded weights (temporal_resample.hip, cvvdp_fir_resampled_yuv)
+struct ResampleArgs {
+  FirArgs f;                   // src, sf, dtype, dm, yuv, W, P as for the other temporal kernels; the rest unused
+  int32_t n_src[2];            // source frames handed in per side
+  int32_t n_out, depth;        // output frames; window depth S of the weights
+  const float* weights[2];     // [n_out][4][depth], index = age of the source frame (0 = newest held)
+  const int32_t* emit[2];      // [n_out] source step after which output n is emitted, non-decreasing
+  float* out[2];               // [4][n_out][P]
+};
+static_assert(sizeof(ResampleArgs) <= 4096, "kernel arguments of the resampling temporal kernel");
+inline bool fir_resampled_has_window(int depth) { return depth == 8 || depth == 12 || depth == 18 || depth == 26; }
+void launch_fir_resampled(const ResampleArgs& a, bool generic, hipStream_t s);
+// core.cpp: argument checks and kernel arguments of cvvdp_fir_resampled_yuv; the error of a launch
+int fir_resampled_prepare(cvvdp_handle* h, const void* t, const void* r, const cvvdp_yuv_format* fmt, int32_t H, int32_t W,
+                          const int32_t n_src[2], int32_t depth, const float* w_t, const float* w_r, const int32_t* e_t, const int32_t* e_r,
+                          int32_t n_out, float* out_t, float* out_r, ResampleArgs& a);
+int fir_resampled_check_launch(cvvdp_handle* h);
+
 // ---------------------------------------------------------------- gaussian pyramid reduce (K2)
 struct ReduceArgs {
   const float* in;   // [planes*items][H*W]

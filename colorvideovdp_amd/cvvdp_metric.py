@@ -346,6 +346,10 @@ class cvvdp(vq_metric):
         inner = getattr(vid_source, "vs", None)             # video_source_file wraps the source that does the work (video_source_file.py:755-820)
         if isinstance(inner, video_source):
             vid_source = inner
+        if hasattr(vid_source, "set_temporal_filters"):
+            # a source that filters in time itself (video_source_temp_resample_file) does it with the metric's filters and padding
+            vid_source.set_temporal_filters(hs.temporal_filters(vid_source.get_frames_per_second(), self.parameters["beta_tf"], self.parameters["sigma_tf"]),
+                                            self.temp_padding)
         height, width, N_frames = vid_source.get_video_size()
         batch_sz = vid_source.get_batch_size()
         if batch_sz > 1 and self.do_heatmap:

@@ -235,6 +235,27 @@ int cvvdp_unpack_yuv_resized(cvvdp_handle* h, const void* dev_codes, const cvvdp
                              int32_t src_height, int32_t n_frames, int32_t dst_width, int32_t dst_height, int32_t mode, float* dev_tmp,
                              float* dev_rgb, void* stream);
 
+/* --temp-resample (video_source_temp_resample_file, video_source_file.py:482-543): the reference resamples clips of different frame
+ * rates to a common rate by REPEATING frames and runs the temporal FIR (cvvdp_metric.py:453-560) at that rate.  This entry computes the
+ * filtered frames from the SOURCE frames: a frame shown r times contributes its value times the sum of the r taps that fall on it, so
+ * the caller folds the taps per distinct source frame (colorvideovdp_amd/temp_resample_plan.py) and every source frame is read and
+ * converted (Y'CbCr unpack, display model, DKL: as cvvdp_process_block_yuv) exactly once.
+ *   dev_test/dev_ref     n_src[side] source frames per side (layout and fmt as for cvvdp_process_block_yuv); step i = frame i
+ *   depth                S: how many source frames a window holds
+ *   dev_weights_*        float [n_out][4][S]: weights[n][c][age] multiplies, for output frame n and channel c, the source frame of step
+ *                        emit[n] - age (0 for steps before 0 and for frames the output does not use)
+ *   dev_emit_*           int32 [n_out], non-decreasing, < n_src[side]: the step after which output frame n is complete
+ *   dev_out_*            float [1, 4, n_out, H, W] per side: Y-sustained, RG, YV, Y-transient = the 'DKLd65_trans' frames
+ *                        cvvdp_process_block_filtered takes
+ *   generic              0: register-window kernel where S is one of 8, 12, 18, 26, else (or 1: always) the generic kernel, which
+ *                        re-converts the frames of every output (any S; same sums, slower)
+ * Results do not depend on how a clip is cut into calls as long as emit[n] - (step of a source frame) is the same in every cut.
+ * Needs no configured clip and touches no handle state (only the handle's display model).  ABI 14: added, nothing else changed. */
+int cvvdp_fir_resampled_yuv(cvvdp_handle* h, const void* dev_test, const void* dev_ref, const cvvdp_yuv_format* fmt, int32_t height,
+                            int32_t width, const int32_t n_src[2], int32_t depth, const float* dev_weights_test,
+                            const float* dev_weights_ref, const int32_t* dev_emit_test, const int32_t* dev_emit_ref, int32_t n_out,
+                            int32_t generic, float* dev_out_test, float* dev_out_ref, void* stream);
+
 /* PSNR metrics (pycvvdp/psnr_metric.py): psnr_rgb (:15-55), pu_psnr_y (:60-112), pu_psnr_rgb2020 (:115-123).  Per frame the reference
  * converts both frames with the source's display model (video_source.py:320-346, display_model.py:206-273) and adds
  * mean((T - R)^2 over C, H, W) to mse[b] (psnr_metric.py:36-43, :82-92).  cvvdp_pixel_sse does that for n_frames frames in one pass:
