@@ -14,7 +14,7 @@
 // Each kind needs <= 128 VGPRs, so a CU holds two 8-wave blocks = four waves per SIMD, and -- waves being dealt to the SIMDs round
 // robin -- every SIMD gets the front and the back wave of one channel of each block: the work per SIMD is what it was, but a wave's
 // chain is half as long and three other waves stand by.  Same two barriers per row; per-row hand-offs are double-buffered by row
-// parity (s_ve, s_g).  LDS: 65.8 KB per block (k_band4f: 50) -- two blocks per CU fit the 160 KB.
+// parity (s_ve, s_g).  LDS: 71.5 - 75.5 KB per block (k_band4f: 50) -- two blocks per CU fit the 160 KB (static_assert below).
 //
 // The arithmetic is k_band4f<4, 0>'s, operation for operation (same FMA chains, same order): the two kernels' level-(l+1) planes are
 // bit-identical and their partial sums agree to the last bit -- they are two separately compiled kernels, and the compiler contracts a
@@ -80,9 +80,14 @@ struct __attribute__((packed, aligned(4))) s_u4 { float x, y, z, w; };     // 16
 
 // The block's LDS (a struct handed to the body: the kernel instantiates the body twice -- strips away from the image border and strips AT
 // it -- and function-local __shared__ arrays of two instantiations would be allocated twice)
+// LATE: the plain kernels pool row r-7 in PHASE 2 of row r's step (band4s_body, BACK: the row step's order).  The pooled row's Mq of all
+// four channels (s_q) and its |T'-R'| (s_d) must then outlive what phase 1 / phase 2 of the same step write: s_q has two buffers by row
+// parity and the lane-private ring of s_d an eighth row.  +7.9 KB: 75 312 bytes per block, two blocks per CU (160 KB) as before.
 template <bool HEAT, bool FEAT>
 struct S4Lds {
   static constexpr int NCH = 4, NP = 8;
+  static constexpr bool LATE = !HEAT && !FEAT;
+  static constexpr int NQ = LATE ? 2 : 1, ND = LATE ? S_R + 2 : S_R + 1;
   __attribute__((aligned(16))) float s_h[HEAT ? NCH : 1][HEAT ? 256 : 4];   // heat-map terms of the pooled row, per channel
   // FEAT: the column sums of D and D^2 live in LDS (lane-private: no barrier) -- with all 24 sums in registers the back waves spilled
   // eight constants and reloaded three of them per row from scratch (level 0 of 4K x 64: 10.5 ms against 7.2 of the plain kernel)
@@ -92,10 +97,12 @@ struct S4Lds {
   __attribute__((aligned(16))) float s_lum[2][256];               // 1/L_T, 1/L_R
   __attribute__((aligned(16))) float s_S[NCH][256];
   __attribute__((aligned(16))) float s_m[NCH][256];
-  __attribute__((aligned(16))) float s_q[NCH][256];
-  __attribute__((aligned(16))) float s_d[S_R + 1][NCH][S_SW];     // lane-private ring of |T'-R'| + eps
+  __attribute__((aligned(16))) float s_q[NQ][NCH][256];           // Mq rows (LATE: by row parity)
+  __attribute__((aligned(16))) float s_d[ND][NCH][S_SW];          // lane-private ring of |T'-R'| + eps
   __attribute__((aligned(16))) float2 s_lut[NCH][CVVDP_CSF_NODES];
 };
+static_assert(sizeof(S4Lds<false, false>) <= 80 * 1024 && sizeof(S4Lds<true, false>) <= 80 * 1024 && sizeof(S4Lds<false, true>) <= 80 * 1024,
+              "two blocks per CU (four waves per SIMD) need at most 80 KB of LDS each");
 
 // EDGE (round 5): the strips that touch the image's left or right border, W % 4 == 0 (band4f.hip EDGE == 1: zero masks of the reduce's
 // padding, the first / last column's extra taps, coarse-column replicas by lane reads, the blur's reflect padding written as mirrors,
@@ -105,6 +112,8 @@ struct S4Lds {
 template <bool HEAT, bool FEAT, bool EDGE>
 __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>& L, const int strip, const int seg, const int item) {
   constexpr int NCH = 4, NP = 8;
+  constexpr bool LATE = S4Lds<HEAT, FEAT>::LATE;
+  constexpr int ND = S4Lds<HEAT, FEAT>::ND;
   auto& s_h = L.s_h; auto& s_fd = L.s_fd; auto& s_ve = L.s_ve; auto& s_g = L.s_g; auto& s_lum = L.s_lum; auto& s_S = L.s_S;
   auto& s_m = L.s_m; auto& s_q = L.s_q; auto& s_d = L.s_d; auto& s_lut = L.s_lut;
 
@@ -533,11 +542,11 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
     for (int k = 0; k < S_BW; ++k) wr[k] = a.blur[(k + 2 * S_BW - 1 - n0) % S_BW];
     float acc = 0.0f;
 
-    // pooling stage of centre row y (band4.hip stage3c)
-    auto stage3c = [&](int k7) {
-      const sf4 q0 = s_lds_read4(&s_q[0][4 * j]), q1 = s_lds_read4(&s_q[1][4 * j]), q2 = s_lds_read4(&s_q[2][4 * j]);
-      const sf4 q3 = s_lds_read4(&s_q[3][4 * j]);
-      const sf4 d = s_lds_read4(&s_d[k7][c][4 * j - S_HALO]);
+    // pooling stage of centre row y (band4.hip stage3c): kd = its row of s_d, qb = its buffer of s_q
+    auto stage3c = [&](int kd, int qb) {
+      const sf4 q0 = s_lds_read4(&s_q[qb][0][4 * j]), q1 = s_lds_read4(&s_q[qb][1][4 * j]), q2 = s_lds_read4(&s_q[qb][2][4 * j]);
+      const sf4 q3 = s_lds_read4(&s_q[qb][3][4 * j]);
+      const sf4 d = s_lds_read4(&s_d[kd][c][4 * j - S_HALO]);
       float De[4], Dh[4];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -576,9 +585,9 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
         }
       }
     };
-    // vertical 13-tap blur of the window -> Mq = (blur + eps)^q -> s_q; then the weights rotate
-    auto vblur = [&](int yc) {
-      if (interior && yc >= ys) {
+    // vertical 13-tap blur of the window -> Mq = (blur + eps)^q -> s_q[qb]; then the weights rotate
+    auto vblur_row = [&](int qb) {
+      {
 #ifdef S_DIAG_VB4      // timing variant: four dependent chains instead of two (results differ in the last bit)
         v2f va = kEps, vb = kEps, va1 = 0.0f, vb1 = 0.0f;
 #pragma unroll
@@ -601,26 +610,58 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
         float Mq[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) Mq[i] = fast_pow(v[i], qc);
-        s_lds_write4(&s_q[c][4 * j], Mq);
+        s_lds_write4(&s_q[qb][c][4 * j], Mq);
       }
+    };
+    auto vblur_rot = [&]() {
       const float last = wr[S_BW - 1];
 #pragma unroll
       for (int k = S_BW - 1; k > 0; --k) wr[k] = wr[k - 1];
       wr[0] = last;
     };
+    auto vblur = [&](int yc) {
+      if (interior && yc >= ys) vblur_row(0);
+      vblur_rot();
+    };
+    // LATE, phase 2 of a row step: the vertical blur of centre row yc and the pooling stage of row yc-1, whose Mq rows phase 2 of the
+    // step before wrote into the other buffer of s_q.  In the steady state both sit under one condition: one basic block, in which the
+    // blur's multiply-add chains and the pooling's pow / rcp chains can be interleaved.
+    auto blur_pool = [&](int yc, int qb, int kd_prev) {
+      if (interior) {
+        if (yc - 1 >= ys) {
+          vblur_row(qb);
+          stage3c(kd_prev, qb ^ 1);
+        } else if (yc >= ys) {
+          vblur_row(qb);
+        }
+      }
+      vblur_rot();
+    };
 
     __syncthreads();        // (front: prologue -> s_ve[0], s_g[0])
     __syncthreads();        // (front: luminance terms of row r_start)
 
-    int slot = n0, k7 = 0;
+    // THE ROW STEP'S ORDER.  Row r's step pools row yprev = r-7.  Pooling needs nothing phase 1 of the step produces, and the back wave
+    // is the longer of the pair up to the first barrier and the shorter up to the second: the plain kernels (LATE) pool behind the
+    // first barrier, beside the vertical blur of row r-6, where the wave would otherwise wait for the front's luminance terms.
+    //   s_q: vblur(r-6) writes buffer (r-6) & 1 while the pooling reads buffer (r-7) & 1, written in phase 2 of step r-1 and next
+    //        written in phase 2 of step r+1 -- two barriers either side.
+    //   s_d: row r goes into ring row kd in phase 1; row r-7 is the next ring row (of eight), overwritten in phase 1 of step r+1 by the
+    //        same lane.
+    // _heat / _feat keep the pooling in phase 1 (heat_row reads s_h one barrier after stage3c, and moving it needs another barrier in the
+    // epilogue of both roles; _feat has no register to spare): one buffer of s_q, seven rows of s_d, as before.
+    int slot = n0, kd = 0;
     uint32_t r_mn = 0x7F7FFFFFu, r_mx = 0u;
-    // one real row r (0 <= r < H)
+    // one real row r (0 <= r < H); ODD = its parity (r_start is even)
     auto step = [&](int r, auto odd_) {
       constexpr bool ODD = decltype(odd_)::value;
       // ================= phase 1
       const int yprev = r - 1 - S_R;
-      if (interior && yprev >= ys) stage3c(k7);
-      feat_d_row(yprev);
+      const int kn = kd == ND - 1 ? 0 : kd + 1;
+      if constexpr (!LATE) {
+        if (interior && yprev >= ys) stage3c(kd, 0);
+        feat_d_row(yprev);
+      }
       const bool feat_row = FEAT && r >= ys && r < ye;  // (scalar) row r belongs to this segment: its |T'|, |R'| are counted
       if (in_img) {                                     // (EDGE == 0: every lane)
         float exT[4], exR[4];
@@ -658,7 +699,7 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
           d[i] = fabsf(ct - cr) * S + kEps;                                        // |T'-R'| + eps (:855, safe_pow)
         }
         s_lds_write4(&s_m[c][4 * j], m);
-        if (interior) s_lds_write4(&s_d[k7][c][4 * j - S_HALO], d);
+        if (interior) s_lds_write4(&s_d[kd][c][4 * j - S_HALO], d);
         if constexpr (FEAT) {
           if (feat_row) {
 #pragma unroll
@@ -722,17 +763,24 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
       }
       S_SYNC();
       // ================= phase 2
-      heat_row(yprev);
-      vblur(r - S_R);
+      if constexpr (LATE) {
+        blur_pool(r - S_R, ODD ? 1 : 0, kn);
+      } else {
+        heat_row(yprev);
+        vblur(r - S_R);
+      }
       slot = slot == S_BW - 1 ? 0 : slot + 1;
-      k7 = k7 == S_R ? 0 : k7 + 1;
+      kd = kn;
       S_SYNC();
     };
     // one reflected row below the image (r >= H): its horizontally blurred row is that of row 2(H-1) - r, still in the window
     auto tail_step = [&](int r) {
       const int yprev = r - 1 - S_R;
-      if (interior && yprev >= ys) stage3c(k7);
-      feat_d_row(yprev);
+      const int kn = kd == ND - 1 ? 0 : kd + 1;
+      if constexpr (!LATE) {
+        if (interior && yprev >= ys) stage3c(kd, 0);
+        feat_d_row(yprev);
+      }
       S_SYNC();
       heat_row(yprev);
       if (interior) {
@@ -741,9 +789,10 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
         const float h0 = winA[2 * src], h1 = winA[2 * src + 1], h2 = winB[2 * src], h3 = winB[2 * src + 1];
         winA[2 * slot] = h0; winA[2 * slot + 1] = h1; winB[2 * slot] = h2; winB[2 * slot + 1] = h3;
       }
-      vblur(r - S_R);
+      if constexpr (LATE) blur_pool(r - S_R, r & 1, kn);
+      else vblur(r - S_R);
       slot = slot == S_BW - 1 ? 0 : slot + 1;
-      k7 = k7 == S_R ? 0 : k7 + 1;
+      kd = kn;
       S_SYNC();
     };
 
@@ -755,7 +804,7 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
     }
     for (r = rreal; r < rend; ++r) tail_step(r);
     // ---- epilogue: pooling stage of the last centre row
-    if (interior && (ye - 1) >= ys) stage3c(k7);
+    if (interior && (ye - 1) >= ys) stage3c(LATE ? (kd == ND - 1 ? 0 : kd + 1) : kd, LATE ? (ye - 1) & 1 : 0);
     if constexpr (FEAT) {
       if ((ye - 1) >= ys) {
         const sf4 fd = s_lds_read4(&s_fd[0][c][4 * j]), fd2 = s_lds_read4(&s_fd[1][c][4 * j]);
