@@ -14,15 +14,19 @@ Differences that are deliberate:
     reference lets them depend on the block size).
   * optional frame-range sharding over torch.distributed (RCCL): see `set_frame_sharding`.
 """
+import collections
+import concurrent.futures
 import ctypes
 import json
 import math
+import time
 
 import numpy as np
 import torch
 
 from . import _capi
 from . import host_setup as hs
+from ._frames import batch_strides, yuv_block_resized
 from .config import config_files, json2dict, load_config
 from .display_model import vvdp_display_geometry, vvdp_display_photo_eotf, vvdp_display_photometry
 from .sharding import all_gather_frames, plan_frame_shard
@@ -65,6 +69,141 @@ class _SequentialFrames:
         for f in [f for f in self.frames if f < a]:     # blocks move forward: nothing before this block's first frame comes back
             del self.frames[f]
         return t, r, _capi.F32_DKL
+
+
+_Route = collections.namedtuple("_Route", "height width n_total B L rho_band is_image is_yuv yuv_resized generic prefiltered nch C code probe_t probe_r")
+
+
+class _HeatmapOut:
+    """Where the heat map of one _score_range call goes: `fetch(ff, n)` takes the n frames scored last (frame ff of the range onwards)
+    off the core, `finish()` returns when all of them have arrived; `heatmap` is the whole clip's map, or None with a sink.  What is
+    worth keeping between calls (page-locked buffers, the copy stream) stays on the metric `m`: _hm_base, _hm_stage, _hm_stream."""
+
+    def __init__(self, m, sink, first, count, height, width, piece, stream):
+        self.m, self.sink, self.first, self.size, self.stream = m, sink, first, (height, width), stream
+        self.hm_ch = 1 if m.heatmap == "raw" else 3
+        self.heatmap = self.copy_stream = self.stage = self.pool = None
+        self.pending, self.slot = [], 0
+        # A sink that writes 8-bit frames anyway (PNG, ffmpeg) sets `wants_uint8`: the conversion the reference's writers do on
+        # the host is then done by the heat-map kernel, and 3 instead of 6 bytes per pixel cross PCIe
+        self.u8 = sink is not None and bool(getattr(sink, "wants_uint8", False))
+        if sink is not None and getattr(sink, "wants_device", False):
+            # A sink that consumes the frames ON THE GPU (statistics, a device-side encoder, a later bulk copy) sets `wants_device`:
+            # it is called with the device tensor of each piece, on the current stream, and nothing crosses PCIe here.  (8K x 256
+            # frames of 8-bit RGB are 25.5 GB: 0.49 s of a PCIe 5 x16 link at the 52 GB/s it sustains -- more than all the kernels.)
+            self.stage = "device"
+        elif sink is not None:
+            # Streaming (SURVEY 8f N3): a ring of page-locked staging buffers of one piece each; piece k is handed to the sink while
+            # the kernels of the pieces after it run.  Host memory is bounded by `heatmap_stage_buffers` pieces whatever the clip length.
+            # Four buffers since round 6 (two before): the kernels of an 8K piece take 21 ms and its 8-bit frames 31 ms of the PCIe link,
+            # so the link is the bound -- and with two buffers it ran dry at every temporal block boundary, where the next piece is
+            # 38 ms away (the block's temporal kernel + the piece's bands) while only one piece was queued: 8K x 256 took 564 ms for 490 ms
+            # of copying (VERDICT r5 weak #5).  With a backlog of up to three pieces the copy engine always has work.
+            stage = getattr(m, "_hm_stage", None)
+            n_stage = max(2, int(getattr(m, "heatmap_stage_buffers", 4)))
+            need = self.hm_ch * piece * height * width * (1 if self.u8 else 2)                              # bytes per piece
+            if stage is None or len(stage) != n_stage or stage[0].numel() < need:
+                m._hm_stage = None                                                                          # (unpin the old ring first)
+                stage = m._hm_stage = [torch.empty(need, dtype=torch.uint8, device="cpu", pin_memory=True) for _ in range(n_stage)]
+            self.stage = stage
+            self.copy_stream = m._hm_stream = getattr(m, "_hm_stream", None) or m._copy_stream()
+        else:
+            # The reference keeps the whole fp16 heat map on the CPU (cvvdp_metric.py:344).  Page-locked memory
+            # + copies on a side stream keep the D2H traffic (6 B/pixel) off the compute stream.
+            # Page-locking gigabytes costs more than filling them (~60 ms per GB), so the buffer of the previous call is
+            # handed out again when nobody holds a tensor or array on it any more (callers get views: a live view shows
+            # up in the storage's use count).
+            shape = [1, self.hm_ch, count, height, width]
+            base = getattr(m, "_hm_base", None)
+            if base is not None and base.numel() == int(np.prod(shape)) and _storage_is_unshared(base):
+                self.heatmap = base.view(shape)
+                self.copy_stream = m._hm_stream
+            else:
+                m._hm_base = None
+                try:
+                    base = torch.empty(int(np.prod(shape)), dtype=torch.float16, device="cpu", pin_memory=True)   # every frame is written below
+                    self.copy_stream = getattr(m, "_hm_stream", None) or m._copy_stream()
+                    m._hm_base, m._hm_stream = base, self.copy_stream
+                    self.heatmap = base.view(shape)
+                except RuntimeError:
+                    self.heatmap = torch.empty(shape, dtype=torch.float16, device="cpu")
+
+    def _feed_sink(self, ev, frame0, view):
+        torch.cuda.set_device(self.m.device)
+        ev.synchronize()
+        self.sink(frame0, view)
+
+    def _flush(self, keep=0):
+        while len(self.pending) > keep:
+            self.pending.pop(0)[0].result()            # (the piece has been consumed; raises what the sink raised)
+
+    def fetch(self, ff, n):
+        m, lib, hm_ch, (height, width), stage = self.m, _capi.lib(), self.hm_ch, self.size, self.stage
+        host_t = [time.perf_counter()]
+        if self.u8:
+            buf = torch.empty((n, height, width, hm_ch), dtype=torch.uint8, device=m.device)
+            host_t.append(time.perf_counter())
+            _capi.check(m._handle, lib.cvvdp_get_heatmap_rgb8(m._handle, n, buf.data_ptr(), self.stream), "cvvdp_get_heatmap_rgb8")
+            host_t.append(time.perf_counter())
+        else:
+            buf = torch.empty((hm_ch, n, height, width), dtype=torch.float16, device=m.device)
+            _capi.check(m._handle, lib.cvvdp_get_heatmap(m._handle, n, buf.data_ptr(), self.stream), "cvvdp_get_heatmap")
+        current = torch.cuda.current_stream(m.device)
+        if stage == "device":
+            self.sink(self.first + ff, buf if self.u8 else buf.view(1, hm_ch, n, height, width))
+        elif stage is not None:
+            # Host sinks are fed from ONE worker thread, piece by piece in order (round 6): the thread waits for the piece's copy and calls
+            # the sink, while this thread goes on queueing kernels and copies.  A sink that takes as long as a piece's copy (a PNG / ffmpeg
+            # writer; even bench.py's frame means, whose strided reads of 1.6 GB cost 30 ms per 8K piece) used to sit between two
+            # pieces' launches: the D2H stream of configs[4] idled 77 of 550 ms (profiles/r06_d2h_events_timeline.txt).  A staging
+            # buffer is reused only after the sink has returned from the piece that used it; a sink's exception is re-raised here.
+            self._flush(keep=len(stage) - 1)           # the buffer about to be overwritten has been consumed
+            host_t.append(time.perf_counter())
+            slot, self.slot = self.slot, (self.slot + 1) % len(stage)
+            if self.u8:
+                view = stage[slot][:hm_ch * n * height * width].view(n, height, width, hm_ch)
+            else:
+                view = stage[slot][:2 * hm_ch * n * height * width].view(torch.float16).view(1, hm_ch, n, height, width)
+            trace = getattr(m, "d2h_trace", None)             # tools/d2h_events_timeline.py: HIP-event timeline of the D2H stream (a list to fill)
+            if trace is not None:
+                ev_k = torch.cuda.Event(enable_timing=True)
+                ev_k.record(current)                          # the piece's kernels are done here
+            self.copy_stream.wait_stream(current)
+            with torch.cuda.stream(self.copy_stream):
+                if trace is not None:
+                    ev_a = torch.cuda.Event(enable_timing=True)
+                    ev_a.record(self.copy_stream)
+                (view if self.u8 else view[0]).copy_(buf, non_blocking=True)
+                ev = torch.cuda.Event(enable_timing=trace is not None)
+                ev.record(self.copy_stream)
+            if trace is not None:
+                host_t.append(time.perf_counter())
+                trace.append((self.first + ff, n, view.numel() * view.element_size(), ev_k, ev_a, ev, host_t))
+            buf.record_stream(self.copy_stream)
+            if self.pool is None:
+                self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="cvvdp-heatmap-sink")
+            self.pending.append((self.pool.submit(self._feed_sink, ev, self.first + ff, view), self.first + ff, view, slot))
+        elif self.copy_stream is None:
+            for ch in range(hm_ch):
+                self.heatmap[0, ch, ff:ff + n] = buf[ch].cpu()
+        else:
+            # one copy per colour plane: heatmap[0, ch, ff:ff+n] is contiguous on the host, the [3, n, H, W] slice of a
+            # longer clip is not (a strided D2H copy falls off the DMA path: 6x slower end to end)
+            self.copy_stream.wait_stream(current)
+            with torch.cuda.stream(self.copy_stream):
+                for ch in range(hm_ch):
+                    self.heatmap[0, ch, ff:ff + n].copy_(buf[ch], non_blocking=True)
+            buf.record_stream(self.copy_stream)
+
+    def finish(self):
+        if self.stage is not None:
+            try:
+                self._flush()
+            finally:
+                if self.pool is not None:
+                    self.pool.shutdown(wait=True)
+        elif self.copy_stream is not None:
+            self.copy_stream.synchronize()   # the heat map is host data: it must be complete when predict() returns
 
 
 class cvvdp(vq_metric):
@@ -524,23 +663,8 @@ class cvvdp(vq_metric):
         return self._seq_frames(vs).block(a, b)
 
     def _yuv_block_resized(self, vs, a, b, height, width):
-        """Frames [a,b) of a .yuv pair with full_screen_resize: [1,3,n,H,W] fp32 R'G'B' blocks at the display's resolution
-        (cvvdp_unpack_yuv_resized: unpack + torch.nn.functional.interpolate semantics + clip, video_source_yuv.py:333-336)."""
-        lib = _capi.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        out = []
-        for side in range(2):
-            codes, fmt, sw, sh = vs.get_raw_yuv_side(side, a, b, self.device)
-            # a side that already has the target size is not interpolated by the reference: nearest at scale 1 is the identity
-            mode = _capi.RESIZE_MODES[vs.full_screen_resize] if (sw, sh) != (width, height) else _capi.RESIZE_MODES["nearest"]
-            tmp = torch.empty(3 * (b - a) * sh * sw, dtype=torch.float32, device=self.device)
-            rgb = torch.empty((1, 3, b - a, height, width), dtype=torch.float32, device=self.device)
-            rc = lib.cvvdp_unpack_yuv_resized(self._handle, codes.data_ptr(), ctypes.byref(fmt), side, sw, sh, b - a, width, height, mode,
-                                              tmp.data_ptr(), rgb.data_ptr(), stream)
-            _capi.check(self._handle, rc, "cvvdp_unpack_yuv_resized")
-            out.append(rgb)
-            del tmp, codes            # stream-ordered: the caching allocator may reuse them once the kernels are queued
-        return out[0], out[1], _capi.F32
+        """Frames [a,b) of a .yuv pair with full_screen_resize as fp32 R'G'B' at the display's resolution + dtype code (_frames.yuv_block_resized)."""
+        return yuv_block_resized(self._handle, self.device, vs, a, b, height, width) + (_capi.F32,)
 
     def _seq_frames(self, vs, colorspace="DKLd65"):
         sf = getattr(self, "_seq", None)
@@ -573,24 +697,12 @@ class cvvdp(vq_metric):
             return not getattr(vs, "device_resident", True)
         return False
 
-    @staticmethod
-    def _strides(t, r):
-        B = max(t.shape[0], r.shape[0])
-        st, sr = list(t.stride()), list(r.stride())
-        if t.shape[0] == 1 and B > 1:
-            st[0] = 0  # broadcast batch (video_source.py:247-252)
-        if r.shape[0] == 1 and B > 1:
-            sr[0] = 0
-        return (ctypes.c_int64 * 5)(*st), (ctypes.c_int64 * 5)(*sr)
+    _strides = staticmethod(batch_strides)
 
-    def _score_range(self, vs, first, count, heatmap_sink=None):
-        """Q_per_ch [B, C, count, bands] (device tensor) of frames [first, first+count)."""
-        lib = _capi.lib()
-        self._sink_on_device = bool(getattr(heatmap_sink, "wants_device", False))
-        height, width, N_total = vs.get_video_size()
-        B = vs.get_batch_size()
-        is_image = N_total == 1
-        nch = 3 if is_image else 4
+    def _route(self, vs, first):
+        """How the frames of `vs` arrive, and the per-call facts the other steps need."""
+        height, width, n_total = vs.get_video_size()
+        is_image = n_total == 1
         pyr_height, freqs = hs.band_frequencies(width, height, self.pix_per_deg)
         L = pyr_height + 1
         rho_band = freqs.copy()
@@ -605,6 +717,7 @@ class cvvdp(vq_metric):
         if prefiltered and not generic:
             raise vq_exception("is_temporally_filtered is only meaningful for sources that deliver 'DKLd65_trans' frames")
         self._seq = None
+        probe_t = probe_r = code = None
         if is_yuv:
             if is_image:
                 raise vq_exception("single-frame .yuv clips are not supported")
@@ -614,9 +727,15 @@ class cvvdp(vq_metric):
         else:
             probe_t, probe_r, code = self._raw_block(vs, first, first + 1)
             C = probe_t.shape[1]
-        # The clip description (temporal taps, CSF rows per band, block size) depends only on the geometry: repeated
-        # calls on clips of the same shape reuse it, so the first kernel is not held back by ~0.4 ms of host set-up.
-        key = (height, width, N_total, first, count, B, C, is_image, None if is_image else float(vs.get_frames_per_second()), self.heatmap,
+        return _Route(height, width, n_total, vs.get_batch_size(), L, rho_band, is_image, is_yuv, yuv_resized, generic, prefiltered,
+                      3 if is_image else 4, C, code, probe_t, probe_r)
+
+    def _plan_clip(self, vs, rt, first, count):
+        """(cvvdp_clip, filter length, temporal filters) of frames [first, first+count); sets F, filter_len and last_block_frames.
+        The clip description (temporal taps, CSF rows per band, block size) depends only on the geometry: repeated
+        calls on clips of the same shape reuse it, so the first kernel is not held back by ~0.4 ms of host set-up."""
+        height, width, is_image, prefiltered = rt.height, rt.width, rt.is_image, rt.prefiltered
+        key = (height, width, rt.n_total, first, count, rt.B, rt.C, is_image, None if is_image else float(vs.get_frames_per_second()), self.heatmap,
                bool(self.debug_dump), int(self.fuse_mode), int(self.band_layout), self.score_frames, self._sink_on_device, self.block_frames, self.gpu_mem, float(self.pix_per_deg), self._cfg_version, prefiltered, getattr(self, "_feature_out", None) is not None,
                self._host_resident(vs))
         cached = getattr(self, "_clip_cache", None)
@@ -624,43 +743,48 @@ class cvvdp(vq_metric):
             clip, fl, F = cached[1], cached[2], cached[3]
             if not is_image:
                 self.F, self.filter_len, self.last_block_frames = F, fl, clip.block_frames
-        else:
-            clip = _capi.Clip()
-            clip.batch, clip.channels, clip.height, clip.width = B, C, height, width
-            clip.is_video, clip.n_frames, clip.n_levels = int(not is_image), count, L
-            clip.first_frame = first
-            clip.total_frames = N_total
-            clip.heatmap = _capi.HEATMAP[self.heatmap]
-            clip.debug_dump = int(self.debug_dump)
-            clip.fuse_mode = int(self.fuse_mode)
-            clip.band_layout = int(self.band_layout)
-            clip.feature_size = int(math.ceil(self.pix_per_deg)) if getattr(self, "_feature_out", None) is not None else 0   # cvvdp_ml_metric.py:353
-            # device-resident clips: later blocks re-read their fl-1 predecessor frames (like a shard's halo) instead of
-            # a DKL tail written by the previous block: 3.2 GB less HBM traffic per 64-frame 4K block
-            clip.raw_halo = int(not is_image and not self._host_resident(vs) and (is_yuv or isinstance(vs, video_source_array) or hasattr(vs, "get_raw_block")))
-            fl, F = 1, None
-            if not is_image:
-                F = hs.temporal_filters(vs.get_frames_per_second(), self.parameters["beta_tf"], self.parameters["sigma_tf"])
-                self.F = F
-                fl = 1 if prefiltered else F.shape[1]     # pre-filtered frames need no window
-                if fl > _capi.MAX_FILTER_LEN:
-                    raise vq_exception(f"frame rates above {(_capi.MAX_FILTER_LEN - 1) * 4} fps are not supported")
-                self.filter_len = fl
-                taps = np.zeros((4, _capi.MAX_FILTER_LEN), dtype=f32)
-                taps[:, :fl] = F[:, :fl]
-                clip.taps[:] = taps.reshape(-1).tolist()
-                nb = self._pick_block_frames(height * width, B, count, fl, nch, self._host_resident(vs), bool(clip.raw_halo))
-                clip.filter_len, clip.block_frames = fl, nb
-                self.last_block_frames = nb
-                # heat-map clips resident in HBM are scored in pieces of a long temporal block (see _pick_block_frames)
-                piece = self._piece_frames()
-                if self.do_heatmap and clip.raw_halo and not prefiltered and not self.debug_dump and nb > piece:
-                    clip.defer_bands, clip.score_frames = 1, piece
-            rows = np.zeros((_capi.MAX_LEVELS, 4, _capi.CSF_NODES), dtype=f32)
-            for bb in range(L):
-                rows[bb] = self.csf_table.rows(rho_band[bb])
-            clip.csf_rows[:] = rows.reshape(-1).tolist()
-            self._clip_cache = (key, clip, fl, F)
+            return clip, fl, F
+        clip = _capi.Clip()
+        clip.batch, clip.channels, clip.height, clip.width = rt.B, rt.C, height, width
+        clip.is_video, clip.n_frames, clip.n_levels = int(not is_image), count, rt.L
+        clip.first_frame = first
+        clip.total_frames = rt.n_total
+        clip.heatmap = _capi.HEATMAP[self.heatmap]
+        clip.debug_dump = int(self.debug_dump)
+        clip.fuse_mode = int(self.fuse_mode)
+        clip.band_layout = int(self.band_layout)
+        clip.feature_size = int(math.ceil(self.pix_per_deg)) if getattr(self, "_feature_out", None) is not None else 0   # cvvdp_ml_metric.py:353
+        # device-resident clips: later blocks re-read their fl-1 predecessor frames (like a shard's halo) instead of
+        # a DKL tail written by the previous block: 3.2 GB less HBM traffic per 64-frame 4K block
+        clip.raw_halo = int(not is_image and not self._host_resident(vs) and (rt.is_yuv or isinstance(vs, video_source_array) or hasattr(vs, "get_raw_block")))
+        fl, F = 1, None
+        if not is_image:
+            F = hs.temporal_filters(vs.get_frames_per_second(), self.parameters["beta_tf"], self.parameters["sigma_tf"])
+            self.F = F
+            fl = 1 if prefiltered else F.shape[1]     # pre-filtered frames need no window
+            if fl > _capi.MAX_FILTER_LEN:
+                raise vq_exception(f"frame rates above {(_capi.MAX_FILTER_LEN - 1) * 4} fps are not supported")
+            self.filter_len = fl
+            taps = np.zeros((4, _capi.MAX_FILTER_LEN), dtype=f32)
+            taps[:, :fl] = F[:, :fl]
+            clip.taps[:] = taps.reshape(-1).tolist()
+            nb = self._pick_block_frames(height * width, rt.B, count, fl, rt.nch, self._host_resident(vs), bool(clip.raw_halo))
+            clip.filter_len, clip.block_frames = fl, nb
+            self.last_block_frames = nb
+            # heat-map clips resident in HBM are scored in pieces of a long temporal block (see _pick_block_frames)
+            piece = self._piece_frames()
+            if self.do_heatmap and clip.raw_halo and not prefiltered and not self.debug_dump and nb > piece:
+                clip.defer_bands, clip.score_frames = 1, piece
+        rows = np.zeros((_capi.MAX_LEVELS, 4, _capi.CSF_NODES), dtype=f32)
+        for bb in range(rt.L):
+            rows[bb] = self.csf_table.rows(rt.rho_band[bb])
+        clip.csf_rows[:] = rows.reshape(-1).tolist()
+        self._clip_cache = (key, clip, fl, F)
+        return clip, fl, F
+
+    def _bind_workspace(self, clip, is_image):
+        """Configure the core for `clip` and bind a workspace of the size it asks for; sets last_score_frames."""
+        lib = _capi.lib()
         while True:
             _capi.check(self._handle, lib.cvvdp_configure(self._handle, ctypes.byref(clip)), "cvvdp_configure")
             need = lib.cvvdp_workspace_bytes(self._handle)
@@ -683,279 +807,145 @@ class cvvdp(vq_metric):
                     clip.defer_bands, clip.score_frames = 0, 0
         _capi.check(self._handle, lib.cvvdp_bind_workspace(self._handle, self._ws.data_ptr(), self._ws.numel()), "cvvdp_bind_workspace")
         self.last_score_frames = int(clip.score_frames) if clip.defer_bands else 0      # (0: every block scored whole)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        heatmap = None
-        hm_ch = 1 if self.heatmap == "raw" else 3
-        copy_stream = None
-        stage, pending_sink, stage_next = None, [], [0]
-        if self.do_heatmap and heatmap_sink is not None:
-            # Streaming: a ring of page-locked staging buffers of one piece each; piece k is handed to the sink while
-            # the kernels of the pieces after it run.  Host memory is bounded by `heatmap_stage_buffers` pieces whatever the clip length.
-            # Four buffers since round 6 (two before): the kernels of an 8K piece take 21 ms and its 8-bit frames 31 ms of the PCIe link,
-            # so the link is the bound -- and with two buffers it ran dry at every temporal block boundary, where the next piece is
-            # 38 ms away (the block's temporal kernel + the piece's bands) while only one piece was queued: 8K x 256 took 564 ms for 490 ms
-            # of copying.  With a backlog of up to three pieces the copy engine always has work.
-            # A sink that writes 8-bit frames anyway (PNG, ffmpeg) sets `wants_uint8`: the conversion the reference's writers do on
-            # the host is then done by the heat-map kernel, and 3 instead of 6 bytes per pixel cross PCIe
-            nb_max = 1 if is_image else (clip.score_frames if clip.defer_bands else clip.block_frames)
-            sink_u8 = bool(getattr(heatmap_sink, "wants_uint8", False))
-            # A sink that consumes the frames ON THE GPU (statistics, a device-side encoder, a later bulk copy) sets `wants_device`:
-            # it is called with the device tensor of each piece, on the current stream, and nothing crosses PCIe here.  (8K x 256
-            # frames of 8-bit RGB are 25.5 GB: 0.49 s of a PCIe 5 x16 link at the 52 GB/s it sustains -- more than all the kernels.)
-            sink_dev = bool(getattr(heatmap_sink, "wants_device", False))
-            stage = getattr(self, "_hm_stage", None)
-            if sink_dev:
-                stage = "device"
-            else:
-                n_stage = max(2, int(getattr(self, "heatmap_stage_buffers", 4)))
-                need = hm_ch * nb_max * height * width * (1 if sink_u8 else 2)                               # bytes per piece
-                if stage is None or stage == "device" or len(stage) != n_stage or stage[0].numel() < need:
-                    self._hm_stage = None                                                                   # (unpin the old ring first)
-                    stage = self._hm_stage = [torch.empty(need, dtype=torch.uint8, device="cpu", pin_memory=True) for _ in range(n_stage)]
-            if not sink_dev:
-                copy_stream = getattr(self, "_hm_stream", None) or self._copy_stream()
-                self._hm_stream = copy_stream
-        elif self.do_heatmap:
-            # The reference keeps the whole fp16 heat map on the CPU (cvvdp_metric.py:344).  Page-locked memory
-            # + copies on a side stream keep the D2H traffic (6 B/pixel) off the compute stream.
-            # Page-locking gigabytes costs more than filling them (~60 ms per GB), so the buffer of the previous call is
-            # handed out again when nobody holds a tensor or array on it any more (callers get views: a live view shows
-            # up in the storage's use count).
-            shape = [1, hm_ch, count, height, width]
-            base = getattr(self, "_hm_base", None)
-            if base is not None and base.numel() == int(np.prod(shape)) and _storage_is_unshared(base):
-                heatmap = base.view(shape)
-                copy_stream = self._hm_stream
-            else:
-                self._hm_base = None
-                try:
-                    base = torch.empty(int(np.prod(shape)), dtype=torch.float16, device="cpu", pin_memory=True)   # every frame is written below
-                    copy_stream = getattr(self, "_hm_stream", None) or self._copy_stream()
-                    self._hm_base, self._hm_stream = base, copy_stream
-                    heatmap = base.view(shape)
-                except RuntimeError:
-                    heatmap = torch.empty(shape, dtype=torch.float16, device="cpu")
 
-        # Host sinks are fed from ONE worker thread, piece by piece in order (round 6): the thread waits for the piece's copy and calls the
-        # sink, while this thread goes on queueing kernels and copies.  A sink that takes as long as a piece's copy (a PNG / ffmpeg
-        # writer; even bench.py's frame means, whose strided reads of 1.6 GB cost 30 ms per 8K piece) used to sit between two
-        # pieces' launches: the D2H stream of configs[4] idled 77 of 550 ms (profiles/r06_d2h_events_timeline.txt).  A staging
-        # buffer is reused only after the sink has returned from the piece that used it; a sink's exception is re-raised here.
-        sink_pool = [None]
+    def _alloc_features(self, rt, clip, count):
+        """The per-band feature tensors of extract_features (`_feature_out`, a list to fill), if this call is to produce them."""
+        if getattr(self, "_feature_out", None) is None:
+            return
+        fs = int(clip.feature_size)
+        lvl = [(rt.height, rt.width)]
+        for _ in range(rt.L - 1):
+            lvl.append(((lvl[-1][0] + 1) // 2, (lvl[-1][1] + 1) // 2))
+        self._feature_out[:] = [torch.empty((count * rt.B, (h + fs - 1) // fs, (w + fs - 1) // fs, rt.nch, 6), dtype=torch.float32, device=self.device)
+                                for h, w in lvl]
 
-        def _feed_sink(ev, frame0, view):
-            torch.cuda.set_device(self.device)
-            ev.synchronize()
-            heatmap_sink(frame0, view)
+    def _fetch_outputs(self, rt, out, ff, n, stream, heatmap=True):
+        """Heat map and features of the n frames scored last, which start at frame `ff` of the range."""
+        if out is not None and heatmap:
+            out.fetch(ff, n)
+        if getattr(self, "_feature_out", None) is not None:
+            for bb in range(rt.L):
+                dst = self._feature_out[bb][ff * rt.B:(ff + n) * rt.B]
+                _capi.check(self._handle, _capi.lib().cvvdp_get_features(self._handle, bb, n, dst.data_ptr(), stream), "cvvdp_get_features")
 
-        def flush_sink(keep=0):
-            while len(pending_sink) > keep:
-                pending_sink.pop(0)[0].result()            # (the piece has been consumed; raises what the sink raised)
+    def _fetch(self, vs, rt, blk):
+        _, _, lo, hi, _ = blk
+        if rt.yuv_resized:
+            return self._yuv_block_resized(vs, lo, hi, rt.height, rt.width)
+        if rt.is_yuv:
+            return vs.get_raw_yuv_block(lo, hi, self.device)
+        return self._raw_block(vs, lo, hi)
 
-        def fetch_heatmap(ff, n):
-            import time as _time
-            host_t = [_time.perf_counter()]
-            if stage is not None and sink_u8:
-                buf = torch.empty((n, height, width, hm_ch), dtype=torch.uint8, device=self.device)
-                host_t.append(_time.perf_counter())
-                _capi.check(self._handle, lib.cvvdp_get_heatmap_rgb8(self._handle, n, buf.data_ptr(), stream), "cvvdp_get_heatmap_rgb8")
-                host_t.append(_time.perf_counter())
-            else:
-                buf = torch.empty((hm_ch, n, height, width), dtype=torch.float16, device=self.device)
-                _capi.check(self._handle, lib.cvvdp_get_heatmap(self._handle, n, buf.data_ptr(), stream), "cvvdp_get_heatmap")
-            if stage == "device":
-                heatmap_sink(first + ff, buf if sink_u8 else buf.view(1, hm_ch, n, height, width))
-                return
-            if stage is not None:
-                flush_sink(keep=len(stage) - 1)            # the buffer about to be overwritten has been consumed
-                host_t.append(_time.perf_counter())
-                slot = stage_next[0]
-                stage_next[0] = (slot + 1) % len(stage)
-                dst = stage[slot]
-                if sink_u8:
-                    view = dst[:hm_ch * n * height * width].view(n, height, width, hm_ch)
+    def _fetch_on(self, h2d, dev_index, vs, rt, blk):
+        torch.cuda.set_device(dev_index)   # the current device is per thread
+        with torch.cuda.stream(h2d):
+            out = self._fetch(vs, rt, blk)
+            ev = torch.cuda.Event()
+            ev.record(h2d)
+        return out, ev
+
+    def _fetched(self, vs, rt, blocks):
+        """(blk, test, reference, dtype code or Y'CbCr format) of every block, in order.  Clips that live on the host cross PCIe one block
+        ahead: a worker thread uploads block k+1 on a side stream while the caller queues the kernels of block k (the copy blocks its
+        thread, not the GPU)."""
+        if not (len(blocks) > 1 and self._host_resident(vs)):
+            for blk in blocks:
+                t, r, third = self._fetch(vs, rt, blk)
+                yield blk, t, r, third
+                del t, r
+            return
+        h2d = self._copy_stream()
+        main_stream = torch.cuda.current_stream(self.device)
+        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+        try:
+            pending = pool.submit(self._fetch_on, h2d, dev_index, vs, rt, blocks[0])
+            for i, blk in enumerate(blocks):
+                (t, r, third), ev = pending.result()
+                pending = pool.submit(self._fetch_on, h2d, dev_index, vs, rt, blocks[i + 1]) if i + 1 < len(blocks) else None
+                main_stream.wait_event(ev)
+                t.record_stream(main_stream)
+                r.record_stream(main_stream)
+                yield blk, t, r, third
+                del t, r
+        finally:
+            pool.shutdown(wait=True)
+
+    def _run_prefiltered(self, vs, rt, first, count, nb, out, stream):
+        seq = self._seq_frames(vs, "DKLd65_trans")
+        for ff in range(first, first + count, nb):
+            n = min(nb, first + count - ff)
+            t, r, _ = seq.block(ff, ff + n, reference_first=True)
+            if t.shape[1] != 4:
+                raise vq_exception("a temporally filtered source must deliver 4-channel 'DKLd65_trans' frames")
+            st, sr = self._strides(t, r)
+            rc = _capi.lib().cvvdp_process_block_filtered(self._handle, t.data_ptr(), r.data_ptr(), st, sr, n, ff - first, stream)
+            _capi.check(self._handle, rc, "cvvdp_process_block_filtered")
+            self._fetch_outputs(rt, out, ff - first, n, stream)
+            del t, r
+
+    def _run_blocks(self, vs, rt, clip, blocks, first, out, stream):
+        lib = _capi.lib()
+        fetched = self._fetched(vs, rt, blocks)
+        try:
+            for (ff, n, lo, hi, hist), t, r, third in fetched:
+                hist_c = (ctypes.c_int32 * max(len(hist), 1))(*hist)
+                if rt.is_yuv and not rt.yuv_resized:
+                    rc = lib.cvvdp_process_block_yuv(self._handle, t.data_ptr(), r.data_ptr(), ctypes.byref(third), ff - lo, hist_c, n,
+                                                     ff - first, stream)
+                    _capi.check(self._handle, rc, "cvvdp_process_block_yuv")
                 else:
-                    view = dst[:2 * hm_ch * n * height * width].view(torch.float16).view(1, hm_ch, n, height, width)
-                trace = getattr(self, "d2h_trace", None)          # tools/d2h_events_timeline.py: HIP-event timeline of the D2H stream (a list to fill)
-                if trace is not None:
-                    ev_k = torch.cuda.Event(enable_timing=True)
-                    ev_k.record(torch.cuda.current_stream(self.device))       # the piece's kernels are done here
-                copy_stream.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(copy_stream):
-                    if trace is not None:
-                        ev_a = torch.cuda.Event(enable_timing=True)
-                        ev_a.record(copy_stream)
-                    (view if sink_u8 else view[0]).copy_(buf, non_blocking=True)
-                    ev = torch.cuda.Event(enable_timing=trace is not None)
-                    ev.record(copy_stream)
-                if trace is not None:
-                    host_t.append(_time.perf_counter())
-                    trace.append((first + ff, n, view.numel() * view.element_size(), ev_k, ev_a, ev, host_t))
-                buf.record_stream(copy_stream)
-                if sink_pool[0] is None:
-                    import concurrent.futures
-                    sink_pool[0] = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="cvvdp-heatmap-sink")
-                pending_sink.append((sink_pool[0].submit(_feed_sink, ev, first + ff, view), first + ff, view, slot))
-                return
-            # one copy per colour plane: heatmap[0, ch, ff:ff+n] is contiguous on the host, the [3, n, H, W] slice of a
-            # longer clip is not (a strided D2H copy falls off the DMA path: 6x slower end to end)
-            if copy_stream is None:
-                for ch in range(hm_ch):
-                    heatmap[0, ch, ff:ff + n] = buf[ch].cpu()
-            else:
-                copy_stream.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(copy_stream):
-                    for ch in range(hm_ch):
-                        heatmap[0, ch, ff:ff + n].copy_(buf[ch], non_blocking=True)
-                buf.record_stream(copy_stream)
+                    st, sr = self._strides(t, r)
+                    rc = lib.cvvdp_process_block(self._handle, t.data_ptr(), r.data_ptr(), third, st, sr, ff - lo, hist_c, n, ff - first, stream)
+                    _capi.check(self._handle, rc, "cvvdp_process_block")
+                if clip.defer_bands:
+                    # the block is filtered; bands, pooling and heat maps piece by piece (the copy of a piece overlaps the next one's kernels)
+                    for p0 in range(0, n, clip.score_frames):
+                        m = min(clip.score_frames, n - p0)
+                        _capi.check(self._handle, lib.cvvdp_score_frames(self._handle, p0, m, stream), "cvvdp_score_frames")
+                        out.fetch(ff - first + p0, m)
+                self._fetch_outputs(rt, out, ff - first, n, stream, heatmap=not clip.defer_bands)
+                del t, r  # stream-ordered: safe to release to the caching allocator once the kernels are queued
+        finally:
+            fetched.close()     # (joins the upload worker, also when a block raised)
 
-        feat_out = getattr(self, "_feature_out", None)
-        if feat_out is not None:
-            fs = int(clip.feature_size)
-            lvl = [(height, width)]
-            for _ in range(L - 1):
-                lvl.append(((lvl[-1][0] + 1) // 2, (lvl[-1][1] + 1) // 2))
-            feat_out[:] = [torch.empty((count * B, (h + fs - 1) // fs, (w + fs - 1) // fs, nch, 6), dtype=torch.float32, device=self.device)
-                           for h, w in lvl]
-
-        def fetch_features(ff, n):
-            for bb in range(L):
-                dst = feat_out[bb][ff * B:(ff + n) * B]
-                _capi.check(self._handle, lib.cvvdp_get_features(self._handle, bb, n, dst.data_ptr(), stream), "cvvdp_get_features")
-
-        if is_image:
-            st, sr = self._strides(probe_t, probe_r)
-            rc = lib.cvvdp_put_image(self._handle, probe_t.data_ptr(), probe_r.data_ptr(), code, st, sr, stream)
+    def _score_range(self, vs, first, count, heatmap_sink=None):
+        """Q_per_ch [B, C, count, bands] (device tensor) of frames [first, first+count), the heat map if it is kept whole, rho_band."""
+        lib = _capi.lib()
+        self._sink_on_device = bool(getattr(heatmap_sink, "wants_device", False))
+        rt = self._route(vs, first)
+        clip, fl, _F = self._plan_clip(vs, rt, first, count)
+        self._bind_workspace(clip, rt.is_image)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        out = None
+        if self.do_heatmap:
+            piece = 1 if rt.is_image else (clip.score_frames if clip.defer_bands else clip.block_frames)
+            out = _HeatmapOut(self, heatmap_sink, first, count, rt.height, rt.width, piece, stream)
+        self._alloc_features(rt, clip, count)
+        if rt.is_image:
+            st, sr = self._strides(rt.probe_t, rt.probe_r)
+            rc = lib.cvvdp_put_image(self._handle, rt.probe_t.data_ptr(), rt.probe_r.data_ptr(), rt.code, st, sr, stream)
             _capi.check(self._handle, rc, "cvvdp_put_image")
             _capi.check(self._handle, lib.cvvdp_process_image(self._handle, stream), "cvvdp_process_image")
-            if self.do_heatmap:
-                fetch_heatmap(0, 1)
-            if feat_out is not None:
-                fetch_features(0, 1)
+            self._fetch_outputs(rt, out, 0, 1, stream)
         else:
             nb = clip.block_frames
-
-            def src_index(j):  # temporal padding before frame 0, cvvdp_metric.py:506-529
-                if j >= 0:
-                    return j
-                return 0 if self.temp_padding == "replicate" else hs.symmetric_frame_index(j, N_total)
-
-            if self.temp_padding not in ("replicate", "symmetric"):
-                raise RuntimeError(f'Unknown padding method "{self.temp_padding}"')
-            if prefiltered:
-                seq = self._seq_frames(vs, "DKLd65_trans")
-                for ff in range(first, first + count, nb):
-                    n = min(nb, first + count - ff)
-                    t, r, _ = seq.block(ff, ff + n, reference_first=True)
-                    if t.shape[1] != 4:
-                        raise vq_exception("a temporally filtered source must deliver 4-channel 'DKLd65_trans' frames")
-                    st, sr = self._strides(t, r)
-                    rc = lib.cvvdp_process_block_filtered(self._handle, t.data_ptr(), r.data_ptr(), st, sr, n, ff - first, stream)
-                    _capi.check(self._handle, rc, "cvvdp_process_block_filtered")
-                    if self.do_heatmap:
-                        fetch_heatmap(ff - first, n)
-                    if feat_out is not None:
-                        fetch_features(ff - first, n)
-                    del t, r
-            blocks = []
             # Heat maps streamed to the host from a resident clip: the link is the bound, and its first byte can only leave after the first
             # temporal block's FIR + the first piece's bands -- so the first temporal block is ONE piece long (8K: the D2H stream starts
             # 13 ms earlier; results do not depend on the cut, bit for bit)
-            head = int(clip.score_frames) if (isinstance(stage, list) and clip.defer_bands and clip.raw_halo and 0 < clip.score_frames < nb) else nb
-            cuts, ff = [], first
-            while not prefiltered and ff < first + count:
-                n = min(head if ff == first else nb, first + count - ff)
-                cuts.append((ff, n))
-                ff += n
-            for ff, n in cuts:
-                if ff == first or clip.raw_halo:
-                    # first block of the clip / shard, and every block of a device-resident clip: the fl-1 window
-                    # positions before frame ff are real predecessor / halo frames or temporal padding; all of them
-                    # are raw frames of the block handed in
-                    hist_frames = [src_index(ff - (fl - 1) + k) for k in range(fl - 1)]
-                    lo = min(hist_frames + [ff])
-                    hi = max(hist_frames + [ff + n - 1]) + 1
-                    hist = [f - lo for f in hist_frames]
-                else:
-                    # later blocks: the DKL tail of the previous block is still in the workspace
-                    lo, hi = ff, ff + n
-                    hist = [-1 - k for k in range(fl - 1)]
-                blocks.append((ff, n, lo, hi, hist))
-
-            def fetch(blk):
-                _, _, lo, hi, _ = blk
-                if yuv_resized:
-                    return self._yuv_block_resized(vs, lo, hi, height, width)
-                if is_yuv:
-                    return vs.get_raw_yuv_block(lo, hi, self.device)
-                return self._raw_block(vs, lo, hi)
-
-            # Clips that live on the host cross PCIe one block ahead: a worker thread uploads block k+1 on a side stream
-            # while this thread queues the kernels of block k (the copy blocks its thread, not the GPU).
-            prefetch = len(blocks) > 1 and self._host_resident(vs)
-            if prefetch:
-                import concurrent.futures
-                h2d = self._copy_stream()
-                main_stream = torch.cuda.current_stream(self.device)
-
-                dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-
-                def fetch_async(blk):
-                    torch.cuda.set_device(dev_index)   # the current device is per thread
-                    with torch.cuda.stream(h2d):
-                        out = fetch(blk)
-                        ev = torch.cuda.Event()
-                        ev.record(h2d)
-                    return out, ev
-
-                pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-                pending = pool.submit(fetch_async, blocks[0])
-            try:
-                for i, blk in enumerate(blocks):
-                    ff, n, lo, hi, hist = blk
-                    if prefetch:
-                        (t, r, third), ev = pending.result()
-                        pending = pool.submit(fetch_async, blocks[i + 1]) if i + 1 < len(blocks) else None
-                        main_stream.wait_event(ev)
-                        t.record_stream(main_stream)
-                        r.record_stream(main_stream)
-                    else:
-                        t, r, third = fetch(blk)
-                    hist_c = (ctypes.c_int32 * max(len(hist), 1))(*hist)
-                    if is_yuv and not yuv_resized:
-                        rc = lib.cvvdp_process_block_yuv(self._handle, t.data_ptr(), r.data_ptr(), ctypes.byref(third), ff - lo, hist_c, n,
-                                                         ff - first, stream)
-                        _capi.check(self._handle, rc, "cvvdp_process_block_yuv")
-                    else:
-                        st, sr = self._strides(t, r)
-                        rc = lib.cvvdp_process_block(self._handle, t.data_ptr(), r.data_ptr(), third, st, sr, ff - lo, hist_c, n, ff - first, stream)
-                        _capi.check(self._handle, rc, "cvvdp_process_block")
-                    if clip.defer_bands:
-                        # the block is filtered; bands, pooling and heat maps piece by piece (the copy of a piece overlaps the next one's kernels)
-                        for p0 in range(0, n, clip.score_frames):
-                            m = min(clip.score_frames, n - p0)
-                            _capi.check(self._handle, lib.cvvdp_score_frames(self._handle, p0, m, stream), "cvvdp_score_frames")
-                            fetch_heatmap(ff - first + p0, m)
-                    elif self.do_heatmap:
-                        fetch_heatmap(ff - first, n)
-                    if feat_out is not None:
-                        fetch_features(ff - first, n)
-                    del t, r  # stream-ordered: safe to release to the caching allocator once the kernels are queued
-            finally:
-                if prefetch:
-                    pool.shutdown(wait=True)
-        Q = torch.empty((B, nch, count, L), dtype=torch.float32, device=self.device)
+            ring = out is not None and isinstance(out.stage, list)
+            head = int(clip.score_frames) if (ring and clip.defer_bands and clip.raw_halo and 0 < clip.score_frames < nb) else nb
+            blocks = hs.plan_blocks(first, count, nb, head, fl, clip.raw_halo, rt.n_total, self.temp_padding)   # (refuses an unknown padding)
+            if rt.prefiltered:
+                self._run_prefiltered(vs, rt, first, count, nb, out, stream)
+            else:
+                self._run_blocks(vs, rt, clip, blocks, first, out, stream)
+        Q = torch.empty((rt.B, rt.nch, count, rt.L), dtype=torch.float32, device=self.device)
         _capi.check(self._handle, lib.cvvdp_get_q_per_ch(self._handle, Q.data_ptr(), stream), "cvvdp_get_q_per_ch")
         self._seq = None
-        if stage is not None:
-            try:
-                flush_sink()
-            finally:
-                if sink_pool[0] is not None:
-                    sink_pool[0].shutdown(wait=True)
-        elif copy_stream is not None:
-            copy_stream.synchronize()   # the heat map is host data: it must be complete when predict() returns
-        return Q, heatmap, rho_band
+        if out is not None:
+            out.finish()
+        return Q, (out.heatmap if out is not None else None), rt.rho_band
 
     # ------------------------------------------------------------------ pooling, info, outputs
     def do_pooling_and_jods(self, Q_per_ch):

@@ -78,3 +78,33 @@ def symmetric_frame_index(frame_ind, frame_count):
     if is_even:
         return ((abs(frame_ind) - 1) % (frame_count - 1)) + 1
     return frame_ind % (frame_count - 1)
+
+
+def plan_blocks(first, count, nb, head, fl, raw_halo, n_total, padding):
+    """The temporal blocks of frames [first, first+count) as (ff, n, lo, hi, hist): frames [ff, ff+n) are scored from the fetched
+    run [lo, hi).  The first block is `head` frames long, the others `nb`.  For the first block of the clip / shard, and for every
+    block when `raw_halo` is set (device-resident clips), the fl-1 window positions before frame ff are real predecessor / halo
+    frames or temporal padding (cvvdp_metric.py:506-529): all of them are raw frames of the run, and `hist` holds their offsets
+    into it.  Later blocks otherwise find the DKL tail of the previous block in the workspace: hist = [-1, -2, ...]."""
+    if padding not in ("replicate", "symmetric"):
+        raise RuntimeError(f'Unknown padding method "{padding}"')
+
+    def src_index(j):
+        if j >= 0:
+            return j
+        return 0 if padding == "replicate" else symmetric_frame_index(j, n_total)
+
+    blocks, ff = [], first
+    while ff < first + count:
+        n = min(head if ff == first else nb, first + count - ff)
+        if ff == first or raw_halo:
+            hist_frames = [src_index(ff - (fl - 1) + k) for k in range(fl - 1)]
+            lo = min(hist_frames + [ff])
+            hi = max(hist_frames + [ff + n - 1]) + 1
+            hist = [f - lo for f in hist_frames]
+        else:
+            lo, hi = ff, ff + n
+            hist = [-1 - k for k in range(fl - 1)]
+        blocks.append((ff, n, lo, hi, hist))
+        ff += n
+    return blocks

@@ -12,14 +12,11 @@ The smaller side of a frame must be larger than 160 (ssim.py:212-215; an asserti
 --full-screen-resize.  Quirk Q8 of ssim_metric holds: size_average=True ends in a plain mean over the batch (ssim.py:240-241), so a
 batched call returns ONE number.  A 1-channel source and different batch sizes of test and reference are refused as in ssim_metric.
 """
-import ctypes
-
 import torch
 
 from . import _capi
 from .psnr_metric import _psnr_base
-from .ssim_metric import ssim_scalars
-from .video_source import video_source, video_source_array
+from .ssim_metric import refuse_block, refuse_source, ssim_scalars
 from .vq_metric import register_metric, vq_exception
 
 WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # ssim.py:217-218
@@ -60,32 +57,14 @@ class ms_ssim_metric(_psnr_base):
     def quality_unit(self):
         return ""
 
-    def predict_video_source(self, vid_source, frame_padding="replicate"):
-        inner = getattr(vid_source, "vs", None)           # video_source_file wraps the source that does the work
-        if isinstance(inner, video_source):
-            vid_source = inner
-        vs = vid_source
-        H, W, N = vs.get_video_size()                     # (the display's resolution with full_screen_resize)
-        B = vs.get_batch_size()
+    def _refuse(self, vs, H, W):
         if min(H, W) <= MIN_SIDE:
             raise vq_exception(f"MS-SSIM: frames of {W}x{H}: the smaller side must be larger than {MIN_SIDE} "
                                "(four 2x downsamplings of an 11-tap window)")
-        if isinstance(vs, video_source_array):
-            t, r, _ = vs.raw_arrays()
-            if t.shape[1] != 3:
-                raise vq_exception("MS-SSIM takes luma from three colour channels: a 1-channel (luminance) source has none")
-            if t.shape[0] != r.shape[0]:
-                raise vq_exception(f"MS-SSIM: test has batch size {t.shape[0]}, reference {r.shape[0]}: the reference's ms_ssim() wants equal shapes")
-        if not torch.cuda.is_available():
-            raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
-        is_yuv = hasattr(vs, "get_raw_yuv_block")
-        raw = is_yuv or hasattr(vs, "get_raw_block") or isinstance(vs, video_source_array)
-        # frames are converted with the SOURCE's display model (video_source_dm), as in the PSNR metrics
-        dm = getattr(vs, "dm_photometry", None) if raw else None
-        if dm is None:
-            dm = self.display_photometry
-        h = self._handle(dm)
-        pargs, _ = self._target(dm)
+        refuse_source(vs, "MS-SSIM", "", "ms_ssim")
+
+    def predict_video_source(self, vid_source, frame_padding="replicate"):
+        vs, H, W, N, B, is_yuv, raw, h, pargs, _ = self._open(vid_source, self._refuse)
         args = self._args(pargs)
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
         # the pooled planes and partials of a call, about 2.7 bytes per pixel and batch item: _blocks keeps them below a quarter of the free
@@ -93,10 +72,7 @@ class ms_ssim_metric(_psnr_base):
         scratch_per_frame = int(_capi.lib().cvvdp_pixel_msssim_scratch_bytes(B, 1, H, W))
         with torch.cuda.device(self.device):
             for t, r, code, fmt, C, n in self._blocks(vs, H, W, N, B, is_yuv, raw, pargs, scratch_per_frame):
-                if C != 3:
-                    raise vq_exception(f"MS-SSIM takes luma from three colour channels, the frames have {C}")
-                if fmt is None and t.shape[0] != r.shape[0]:       # (planar Y'CbCr blocks are flat code arrays of one clip)
-                    raise vq_exception(f"MS-SSIM: test has batch size {t.shape[0]}, reference {r.shape[0]}")
+                refuse_block("MS-SSIM", t, r, fmt, C)
                 args.ssim.target = pargs.target     # a generic source hands out converted frames: _blocks switches to AS_IS
                 self._msssim(h, t, r, code, fmt, B, n, H, W, args, acc)
         return (acc[0] / N).to(torch.float32), None
@@ -116,19 +92,11 @@ class ms_ssim_metric(_psnr_base):
         return args
 
     def _msssim(self, h, t, r, code, fmt, B, n, H, W, args, acc, levels=None, scratch=None):
-        lib = _capi.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         per_frame = torch.empty((n, B), dtype=torch.float64, device=self.device)
         if levels is None:
             levels = torch.empty((n, B, LEVELS), dtype=torch.float64, device=self.device)
-        nbytes = lib.cvvdp_pixel_msssim_scratch_bytes(B, n, H, W)
-        if scratch is None:
-            scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
-        st, sr = (None, None) if fmt is not None else self._strides(t, r, B)
-        rc = lib.cvvdp_pixel_msssim(h, t.data_ptr(), r.data_ptr(), code, st, sr, ctypes.byref(fmt) if fmt is not None else None, B, 3, n, H, W,
-                                    ctypes.byref(args), per_frame.data_ptr(), levels.data_ptr(), acc.data_ptr() if acc is not None else None,
-                                    scratch.data_ptr(), nbytes, stream)
-        _capi.check(h, rc, "cvvdp_pixel_msssim")
+        outs = (per_frame.data_ptr(), levels.data_ptr(), acc.data_ptr() if acc is not None else None)
+        self._pixel_call("cvvdp_pixel_msssim", h, t, r, code, fmt, B, 3, n, H, W, args, outs, scratch)
         return per_frame
 
 

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._frames import batch_strides, yuv_block_resized
 from .display_model import vvdp_display_photo_eotf, vvdp_display_photometry
 from .video_source import video_source, video_source_array
 from .vq_metric import register_metric, vq_metric
@@ -144,23 +145,27 @@ class _psnr_base(vq_metric):
             max_I = float(s["pu_100"])
         return a, max_I
 
-    def predict_video_source(self, vid_source, frame_padding="replicate"):
+    def _open(self, vid_source, refuse=None):
+        """The opening of every predict_video_source: (vs, H, W, N, B, is_yuv, raw, handle, cvvdp_psnr_args, max_I).  `refuse(vs, H, W)`
+        raises for sources the metric does not take, before anything touches the GPU."""
         inner = getattr(vid_source, "vs", None)           # video_source_file wraps the source that does the work
-        if isinstance(inner, video_source):
-            vid_source = inner
+        vs = inner if isinstance(inner, video_source) else vid_source
+        H, W, N = vs.get_video_size()                     # (the display's resolution with full_screen_resize)
+        B = vs.get_batch_size()
+        if refuse is not None:
+            refuse(vs, H, W)
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
-        H, W, N = vid_source.get_video_size()
-        B = vid_source.get_batch_size()
-        vs = vid_source
         is_yuv = hasattr(vs, "get_raw_yuv_block")
         raw = is_yuv or hasattr(vs, "get_raw_block") or isinstance(vs, video_source_array)
         # frames are converted with the SOURCE's display model (video_source_dm, as cvvdp_metric.py:363 does)
         dm = getattr(vs, "dm_photometry", None) if raw else None
         if dm is None:
             dm = self.display_photometry
-        h = self._handle(dm)
-        args, max_I = self._target(dm)
+        return (vs, H, W, N, B, is_yuv, raw, self._handle(dm)) + self._target(dm)
+
+    def predict_video_source(self, vid_source, frame_padding="replicate"):
+        vs, H, W, N, B, is_yuv, raw, h, args, max_I = self._open(vid_source)
         mse = torch.zeros(B, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             for t, r, code, fmt, C, n in self._blocks(vs, H, W, N, B, is_yuv, raw, args):
@@ -168,28 +173,24 @@ class _psnr_base(vq_metric):
         psnr = 20 * torch.log10(max_I / torch.sqrt(mse / N))
         return psnr.to(torch.float32), None
 
-    def _sse(self, h, t, r, code, fmt, B, C, n, H, W, args, mse):
+    def _pixel_call(self, name, h, t, r, code, fmt, B, C, n, H, W, args, outs, scratch=None):
+        """One call of a cvvdp_pixel_* entry point on the current stream: scratch sized by its `_scratch_bytes`, tensor strides for
+        arrays or the Y'CbCr format for planar codes, and the device pointers `outs` the entry point fills."""
         lib = _capi.lib()
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        sse = torch.empty((n, B), dtype=torch.float64, device=self.device)
-        nbytes = lib.cvvdp_pixel_sse_scratch_bytes(B, n, H, W)
-        scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
-        if fmt is not None:
-            st = sr = None
-        else:
-            st, sr = self._strides(t, r, B)
-        rc = lib.cvvdp_pixel_sse(h, t.data_ptr(), r.data_ptr(), code, st, sr, ctypes.byref(fmt) if fmt is not None else None, B, C, n, H, W,
-                                 ctypes.byref(args), sse.data_ptr(), mse.data_ptr(), scratch.data_ptr(), nbytes, stream)
-        _capi.check(h, rc, "cvvdp_pixel_sse")
+        nbytes = getattr(lib, name + "_scratch_bytes")(B, n, H, W)
+        if scratch is None:
+            scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
+        st, sr = (None, None) if fmt is not None else self._strides(t, r, B)
+        rc = getattr(lib, name)(h, t.data_ptr(), r.data_ptr(), code, st, sr, ctypes.byref(fmt) if fmt is not None else None, B, C, n, H, W,
+                                ctypes.byref(args), *outs, scratch.data_ptr(), nbytes, stream)
+        _capi.check(h, rc, name)
 
-    @staticmethod
-    def _strides(t, r, B):
-        st, sr = list(t.stride()), list(r.stride())
-        if t.shape[0] == 1 and B > 1:
-            st[0] = 0  # broadcast batch (video_source.py:247-252)
-        if r.shape[0] == 1 and B > 1:
-            sr[0] = 0
-        return (ctypes.c_int64 * 5)(*st), (ctypes.c_int64 * 5)(*sr)
+    def _sse(self, h, t, r, code, fmt, B, C, n, H, W, args, mse):
+        sse = torch.empty((n, B), dtype=torch.float64, device=self.device)
+        self._pixel_call("cvvdp_pixel_sse", h, t, r, code, fmt, B, C, n, H, W, args, (sse.data_ptr(), mse.data_ptr()))
+
+    _strides = staticmethod(batch_strides)
 
     def _block_frames(self, bytes_per_frame, N, resident, scratch_per_frame=0):
         """Frames per call: a device-resident clip is scored in one call; frames that have to be copied or unpacked first come in blocks
@@ -251,23 +252,8 @@ class _psnr_base(vq_metric):
                 yield t, r, _capi.F32, None, t.shape[1], b - a
 
     def _yuv_block_resized(self, vs, a, b, height, width):
-        """Frames [a,b) of a .yuv pair with full_screen_resize (video_source_yuv.py:333-336): [1,3,n,H,W] fp32 R'G'B' at the display's
-        resolution, unpacked and resized on the GPU (cvvdp_unpack_yuv_resized)."""
-        lib = _capi.lib()
-        h = self._handle(vs.dm_photometry)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        out = []
-        for side in range(2):
-            codes, fmt, sw, sh = vs.get_raw_yuv_side(side, a, b, self.device)
-            # a side that already has the target size is not interpolated by the reference: nearest at scale 1 is the identity
-            mode = _capi.RESIZE_MODES[vs.full_screen_resize] if (sw, sh) != (width, height) else _capi.RESIZE_MODES["nearest"]
-            tmp = torch.empty(3 * (b - a) * sh * sw, dtype=torch.float32, device=self.device)
-            rgb = torch.empty((1, 3, b - a, height, width), dtype=torch.float32, device=self.device)
-            rc = lib.cvvdp_unpack_yuv_resized(h, codes.data_ptr(), ctypes.byref(fmt), side, sw, sh, b - a, width, height, mode,
-                                              tmp.data_ptr(), rgb.data_ptr(), stream)
-            _capi.check(h, rc, "cvvdp_unpack_yuv_resized")
-            out.append(rgb)
-        return out[0], out[1]
+        """Frames [a,b) of a .yuv pair with full_screen_resize as fp32 R'G'B' at the display's resolution (_frames.yuv_block_resized)."""
+        return yuv_block_resized(self._handle(vs.dm_photometry), self.device, vs, a, b, height, width)
 
 
 class psnr_rgb(_psnr_base):

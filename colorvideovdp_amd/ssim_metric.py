@@ -14,14 +14,12 @@ here it is refused with a vq_exception.  So are a test and a reference of differ
 ssim.py:131-132; the reference's array source lets a singleton batch through and ssim() then raises) and frames with a height or a
 width of 1 (ssim() squeezes the dimension away and rejects the 3-d tensor, ssim.py:134-139).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _capi
 from .psnr_metric import _psnr_base
-from .video_source import video_source, video_source_array
+from .video_source import video_source_array
 from .vq_metric import register_metric, vq_exception
 
 LUMA = (0.212656, 0.715158, 0.072186)      # ssim_metric.py:10
@@ -41,6 +39,23 @@ def ssim_scalars():
             "luma": np.asarray(LUMA, dtype=np.float32)}
 
 
+def refuse_source(vs, name, one_channel_tail, ref_fn):
+    """The refusals SSIM and MS-SSIM (`name`) share for an array source, each with the metric's own wording."""
+    if isinstance(vs, video_source_array):
+        t, r, _ = vs.raw_arrays()
+        if t.shape[1] != 3:
+            raise vq_exception(f"{name} takes luma from three colour channels: a 1-channel (luminance) source has none{one_channel_tail}")
+        if t.shape[0] != r.shape[0]:
+            raise vq_exception(f"{name}: test has batch size {t.shape[0]}, reference {r.shape[0]}: the reference's {ref_fn}() wants equal shapes")
+
+
+def refuse_block(name, t, r, fmt, C):
+    if C != 3:
+        raise vq_exception(f"{name} takes luma from three colour channels, the frames have {C}")
+    if fmt is None and t.shape[0] != r.shape[0]:       # (planar Y'CbCr blocks are flat code arrays of one clip)
+        raise vq_exception(f"{name}: test has batch size {t.shape[0]}, reference {r.shape[0]}")
+
+
 class ssim_metric(_psnr_base):
     """Plain SSIM on luma (ssim_metric.py:17-58): display-encoded values, PU21-encoded (scaled so that 100 cd/m^2 maps to 1) when the
     display is linear or PQ; window 11, sigma 1.5, data range 1, no non-negativity clamp.  Quirks Q8 and Q9: module docstring."""
@@ -57,32 +72,13 @@ class ssim_metric(_psnr_base):
     def quality_unit(self):
         return ""
 
-    def predict_video_source(self, vid_source, frame_padding="replicate"):
-        inner = getattr(vid_source, "vs", None)           # video_source_file wraps the source that does the work
-        if isinstance(inner, video_source):
-            vid_source = inner
-        vs = vid_source
-        H, W, N = vs.get_video_size()
-        B = vs.get_batch_size()
+    def _refuse(self, vs, H, W):
         if H < 2 or W < 2:
             raise vq_exception(f"SSIM: frames of {W}x{H}: the reference's ssim() drops dimensions of size 1 and rejects what is left")
-        if isinstance(vs, video_source_array):
-            t, r, _ = vs.raw_arrays()
-            if t.shape[1] != 3:
-                raise vq_exception("SSIM takes luma from three colour channels: a 1-channel (luminance) source has none (the reference fails "
-                                   "with an IndexError)")
-            if t.shape[0] != r.shape[0]:
-                raise vq_exception(f"SSIM: test has batch size {t.shape[0]}, reference {r.shape[0]}: the reference's ssim() wants equal shapes")
-        if not torch.cuda.is_available():
-            raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
-        is_yuv = hasattr(vs, "get_raw_yuv_block")
-        raw = is_yuv or hasattr(vs, "get_raw_block") or isinstance(vs, video_source_array)
-        # frames are converted with the SOURCE's display model (video_source_dm), as in the PSNR metrics
-        dm = getattr(vs, "dm_photometry", None) if raw else None
-        if dm is None:
-            dm = self.display_photometry
-        h = self._handle(dm)
-        pargs, _ = self._target(dm)
+        refuse_source(vs, "SSIM", " (the reference fails with an IndexError)", "ssim")
+
+    def predict_video_source(self, vid_source, frame_padding="replicate"):
+        vs, H, W, N, B, is_yuv, raw, h, pargs, _ = self._open(vid_source, self._refuse)
         s = ssim_scalars()
         args = _capi.SsimArgs()
         args.win[:] = s["win"].tolist()
@@ -93,24 +89,14 @@ class ssim_metric(_psnr_base):
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             for t, r, code, fmt, C, n in self._blocks(vs, H, W, N, B, is_yuv, raw, pargs):
-                if C != 3:
-                    raise vq_exception(f"SSIM takes luma from three colour channels, the frames have {C}")
-                if fmt is None and t.shape[0] != r.shape[0]:       # (planar Y'CbCr blocks are flat code arrays of one clip)
-                    raise vq_exception(f"SSIM: test has batch size {t.shape[0]}, reference {r.shape[0]}")
+                refuse_block("SSIM", t, r, fmt, C)
                 args.target = pargs.target          # a generic source hands out converted frames: _blocks switches to AS_IS
                 self._ssim(h, t, r, code, fmt, B, n, H, W, args, acc)
         return (acc[0] / N).to(torch.float32), None
 
     def _ssim(self, h, t, r, code, fmt, B, n, H, W, args, acc):
-        lib = _capi.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         per_frame = torch.empty((n, B), dtype=torch.float64, device=self.device)
-        nbytes = lib.cvvdp_pixel_ssim_scratch_bytes(B, n, H, W)
-        scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
-        st, sr = (None, None) if fmt is not None else self._strides(t, r, B)
-        rc = lib.cvvdp_pixel_ssim(h, t.data_ptr(), r.data_ptr(), code, st, sr, ctypes.byref(fmt) if fmt is not None else None, B, 3, n, H, W,
-                                  ctypes.byref(args), per_frame.data_ptr(), acc.data_ptr(), scratch.data_ptr(), nbytes, stream)
-        _capi.check(h, rc, "cvvdp_pixel_ssim")
+        self._pixel_call("cvvdp_pixel_ssim", h, t, r, code, fmt, B, 3, n, H, W, args, (per_frame.data_ptr(), acc.data_ptr()))
 
 
 register_metric(ssim_metric)
