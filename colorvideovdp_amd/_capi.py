@@ -109,6 +109,21 @@ class MsssimArgs(C.Structure):
     ]
 
 
+PREVIEW_AS_IS, PREVIEW_LINEAR, PREVIEW_PQ = range(3)      # CVVDP_PREVIEW_* targets
+PREVIEW_F32, PREVIEW_RGBE, PREVIEW_RGB48 = range(3)       # CVVDP_PREVIEW_* output formats
+PREVIEW_PIXEL_BYTES = {PREVIEW_F32: 12, PREVIEW_RGBE: 4, PREVIEW_RGB48: 6}
+
+
+class PreviewArgs(C.Structure):
+    _fields_ = [
+        ("target", C.c_int32), ("out_format", C.c_int32),
+        ("rows", C.c_float * 9),
+        ("x0", C.c_int32), ("y0", C.c_int32),
+        ("reserved", C.c_int32),
+        ("dst_stride_row", C.c_int64), ("dst_stride_frame", C.c_int64), ("dst_stride_c", C.c_int64),
+    ]
+
+
 # CVVDP_E_RGBE_*: what cvvdp_rgbe_header / cvvdp_rgbe_decode answer to a file they do not read
 RGBE_E_MAGIC, RGBE_E_XYZE, RGBE_E_ORIENTATION, RGBE_E_SIZE, RGBE_E_BUFFER, RGBE_E_TRUNCATED, RGBE_E_RUN, RGBE_E_SCANLINE_WIDTH, RGBE_E_ZERO_COUNT = \
     range(-101, -110, -1)
@@ -155,6 +170,9 @@ SYMBOLS = {
     "cvvdp_rgbe_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "cvvdp_rgbe_strerror": (C.c_char_p, [C.c_int]),
     "cvvdp_unpack_rgbe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "cvvdp_preview_args_size": (C.c_int32, []),
+    "cvvdp_pixel_preview": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(PreviewArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_process_block_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.c_int32, C.c_int32, C.c_void_p]),
     "cvvdp_get_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -210,6 +228,8 @@ def lib():
             raise ImportError(f"struct layout mismatch: cvvdp_ssim_args is {l.cvvdp_ssim_args_size()} bytes in the library, {C.sizeof(SsimArgs)} in the binding")
         if l.cvvdp_msssim_args_size() != C.sizeof(MsssimArgs):
             raise ImportError(f"struct layout mismatch: cvvdp_msssim_args is {l.cvvdp_msssim_args_size()} bytes in the library, {C.sizeof(MsssimArgs)} in the binding")
+        if l.cvvdp_preview_args_size() != C.sizeof(PreviewArgs):
+            raise ImportError(f"struct layout mismatch: cvvdp_preview_args is {l.cvvdp_preview_args_size()} bytes in the library, {C.sizeof(PreviewArgs)} in the binding")
         # The band kernels' hand-issued loads were checked against the register allocation of the compiler the library was built with
         # (cvvdp_build_info; bench.py prints it in config.library_build).  The HIP runtime in the process is whatever torch's wheel
         # bundles (here 7.0 under a 7.2 toolchain: a minor-version gap is the normal state and says nothing), so only another MAJOR

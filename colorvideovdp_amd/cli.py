@@ -1,8 +1,10 @@
 """Command line of the MI355X build: `python -m colorvideovdp_amd` / `cvvdp` (console entry in pyproject.toml).
 
 Mirrors the reference's command line (pycvvdp/run_cvvdp.py:83-118 arguments, :120-371 run_on_args) for the path this build
-implements: the `cvvdp` metric, the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020`, the SSIM metric `ssim-metric` and the MS-SSIM metric
-`ms-ssim-metric` (`-m cvvdp psnr-rgb ssim-metric ms-ssim-metric ...`, one output line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit; Radiance .hdr for HDR images, e.g. `-d standard_hdr_linear`), planar .yuv clips (the
+implements: the `cvvdp` metric, the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020`, the SSIM metric `ssim-metric`, the MS-SSIM metric
+`ms-ssim-metric` and the display-model previews `dm-preview`, `dm-preview-sbs`, `dm-preview-hdr` and `dm-preview-hdr-sbs` (fake metrics that write
+what the display model makes of both inputs into --output-dir and print -1; dm_preview_metric.py)
+(`-m cvvdp psnr-rgb ssim-metric ms-ssim-metric ...`, one output line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit; Radiance .hdr for HDR images, e.g. `-d standard_hdr_linear`), planar .yuv clips (the
 file name carries size, frame rate, bit depth and chroma format, video_source_yuv.py:8-62) and .npy arrays.  Same options,
 same output lines (`cvvdp=9.1234 [JOD]`, or only the number with --quiet), same side outputs (--result CSV, --features
 JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpeg and the build is GPU-only:
@@ -10,8 +12,8 @@ JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpe
   * the heat map of a VIDEO is streamed block by block: into `<base>_heatmap.mp4` through an ffmpeg pipe (the reference's
     file and codec settings) where an `ffmpeg` executable exists, otherwise into a numbered PNG sequence
     `<base>_heatmap_%05d.png` (`ffmpeg -i <base>_heatmap_%05d.png <base>_heatmap.mp4` converts it); an image gives `<base>_heatmap.png`;
-  * --device must be a cuda device; --temp-padding 'valid', --dump-channels and two of the metrics the reference does not
-    register by default (dm-preview, the cvvdp-ml heads) are not available; --full-screen-resize works for .yuv clips (as in the
+  * --device must be a cuda device; --temp-padding 'valid', --dump-channels, the cvvdp-ml heads and the OpenEXR previews
+    (dm-preview-exr, dm-preview-exr-sbs: dm-preview-hdr and dm-preview-hdr-sbs write the same values as Radiance .hdr) are not available; --full-screen-resize works for .yuv clips (as in the
     reference it is not implemented for images);
   * --temp-resample [X] scores .yuv clips whose file names carry different frame rates (a 30 fps encode against its 60 fps source) at
     min(lcm of the two rates, X or 166) frames per second like the reference (video_source_file.py:482-543), for the cvvdp metric,
@@ -37,6 +39,7 @@ from .cvvdp_metric import cvvdp
 from . import psnr_metric  # noqa: F401  (registers psnr_rgb, pu_psnr_y, pu_psnr_rgb2020)
 from . import ssim_metric  # noqa: F401  (registers ssim_metric)
 from . import ms_ssim_metric  # noqa: F401  (registers ms_ssim_metric)
+from . import dm_preview_metric  # noqa: F401  (registers dm_preview, dm_preview_sbs, dm_preview_hdr, dm_preview_hdr_sbs)
 from .display_model import vvdp_display_geometry, vvdp_display_photometry
 from .video_source_file import IMAGE_EXT, VIDEO_EXT, load_image_as_array, video_source_file
 from .video_source_temp_resample import video_source_temp_resample_file
@@ -72,7 +75,8 @@ _OPTIONS = (
     (("--count-frames",), dict(action="store_true", default=False, help="accepted for compatibility (frame counts of .yuv / .npy inputs are exact)")),
     (("-f", "--full-screen-resize"), dict(choices=["bilinear", "bicubic", "nearest", "area"], default=None,
                                           help="resize test and reference to the display's resolution (.yuv clips; on the GPU, torch.nn.functional.interpolate semantics)")),
-    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, psnr-rgb, pu-psnr-y, pu-psnr-rgb2020, ssim-metric, ms-ssim-metric")),
+    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, psnr-rgb, pu-psnr-y, pu-psnr-rgb2020, ssim-metric, ms-ssim-metric; "
+                                   "dm-preview[-hdr][-sbs] write the display model's output as HDR video / Radiance .hdr files")),
     (("--temp-padding",), dict(choices=["replicate", "symmetric", "valid"], default="symmetric", help="padding before the first frame ('valid': " + _NA + ")")),
     (("--pix-per-deg",), dict(type=float, default=None, help="override the display geometry")),
     (("--fps",), dict(type=float, default=None, help="frame rate: needed for .npy clips and numbered image frames (name_%%04d.png, name_%%04d.hdr), overrides a .yuv file name")),
@@ -193,7 +197,7 @@ def run_on_args(args):
             raise RuntimeError(f"Unknown metric {mm}")
         fv = vq_metric_dict[mm](**metric_arguments(vq_metric_dict[mm], display_photometry=display_photometry, display_geometry=display_geometry,
                                                    device=device, heatmap=args.heatmap, temp_padding=args.temp_padding,
-                                                   config_paths=args.config_paths, gpu_mem=args.gpu_mem, quiet=args.quiet))
+                                                   config_paths=args.config_paths, gpu_mem=args.gpu_mem, quiet=args.quiet, verbose=args.verbose))
         fv.train(False)
         metrics.append(fv)
         info = fv.get_info_string()

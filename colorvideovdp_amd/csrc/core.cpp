@@ -929,6 +929,54 @@ int cvvdp::rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int
   return CVVDP_OK;
 }
 int cvvdp::rgbe_check_launch(cvvdp_handle* h) { return check_launch(h, "unpack_rgbe"); }
+// cvvdp_pixel_preview (preview.hip) up to the launch: the source checks of cvvdp_pixel_sse on one side, then the target, the format and
+// the canvas.  Nothing is launched unless the last pixel of the last frame lies inside dst_bytes.
+int cvvdp::preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref,
+                           int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_preview_args* args, void* dst, size_t dst_bytes,
+                           PreviewArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!src || !args || !dst) return fail(h, CVVDP_E_ARG, "pixel_preview: null argument");
+  if (B != 1) return fail(h, CVVDP_E_ARG, "pixel_preview: B = %d, batches are not previewed", B);
+  if (args->target < CVVDP_PREVIEW_AS_IS || args->target > CVVDP_PREVIEW_PQ) return fail(h, CVVDP_E_ARG, "pixel_preview: target %d unknown", args->target);
+  if (args->out_format < CVVDP_PREVIEW_F32 || args->out_format > CVVDP_PREVIEW_RGB48)
+    return fail(h, CVVDP_E_ARG, "pixel_preview: output format %d unknown", args->out_format);
+  const bool planar = dtype == CVVDP_YUV8 || dtype == CVVDP_YUV16;
+  if (planar && args->target == CVVDP_PREVIEW_AS_IS) return fail(h, CVVDP_E_ARG, "pixel_preview: Y'CbCr frames cannot be taken as they are");
+  if (args->target != CVVDP_PREVIEW_AS_IS)
+    for (int i = 0; i < 9; ++i)
+      if (!std::isfinite(args->rows[i])) return fail(h, CVVDP_E_ARG, "pixel_preview: rows[%d] is not finite", i);
+  a = PreviewArgs{};
+  cvvdp_psnr_args pa{};
+  pa.target = CVVDP_PSNR_AS_IS;
+  // (the result and scratch pointers of the metrics do not exist here: dst stands in for both, the kernel sees neither)
+  if (int rc = pixel_prepare("pixel_preview", 0, h, src, src, dtype, st, st, yuv, 1, C, n_frames, H, W, &pa, static_cast<const double*>(dst), dst, 0, a.p))
+    return rc;
+  a.side = is_ref ? 1 : 0;
+  a.target = args->target; a.format = args->out_format;
+  for (int i = 0; i < 9; ++i) a.rows[i] = args->rows[i];
+  // the canvas: the last pixel index is (n_frames - 1) * sf + (y0 + H - 1) * sr + x0 + W - 1 (+ 2 * sc floats for planes)
+  const int64_t sr = args->dst_stride_row, sf = args->dst_stride_frame, sc = args->out_format == CVVDP_PREVIEW_F32 ? args->dst_stride_c : 0;
+  if (args->x0 < 0 || args->y0 < 0 || sr < (int64_t)args->x0 + W || sf < 0 || sc < 0)
+    return fail(h, CVVDP_E_ARG, "pixel_preview: bad canvas: origin (%d, %d), row stride %lld, frame stride %lld, channel stride %lld for frames of %dx%d",
+                args->x0, args->y0, (long long)sr, (long long)sf, (long long)sc, W, H);
+  const int64_t px_bytes = args->out_format == CVVDP_PREVIEW_RGB48 ? 6 : 4;
+  int64_t last = 0, term = 0, bytes = 0;
+  bool over = __builtin_mul_overflow((int64_t)(n_frames - 1), sf, &last);
+  over = over || __builtin_mul_overflow((int64_t)args->y0 + H - 1, sr, &term) || __builtin_add_overflow(last, term, &last);
+  over = over || __builtin_mul_overflow((int64_t)2, sc, &term) || __builtin_add_overflow(last, term, &last);
+  over = over || __builtin_add_overflow(last, (int64_t)args->x0 + W, &last);        // one past the last pixel
+  over = over || __builtin_mul_overflow(last, px_bytes, &bytes);
+  if (over || (uint64_t)bytes > (uint64_t)dst_bytes)
+    return fail(h, CVVDP_E_ARG, "pixel_preview: the canvas of %zu bytes does not hold %d frames of %dx%d at (%d, %d)", dst_bytes, n_frames, W, H,
+                args->x0, args->y0);
+  const uintptr_t align = args->out_format == CVVDP_PREVIEW_RGB48 ? 2 : 4;
+  if (reinterpret_cast<uintptr_t>(dst) % align) return fail(h, CVVDP_E_ARG, "pixel_preview: canvas pointer not %d-byte aligned", (int)align);
+  a.dst = dst;
+  a.origin = (int64_t)args->y0 * sr + args->x0;
+  a.sr = sr; a.sf = sf; a.sc = sc;
+  return CVVDP_OK;
+}
+int cvvdp::preview_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_preview"); }
 int cvvdp::psnr_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_sse"); }
 // cvvdp_fir_resampled_yuv (temporal_resample.hip) up to the launch: argument checks and the kernel arguments (the entry point lives next to
 // its kernels, like the pixel metrics')

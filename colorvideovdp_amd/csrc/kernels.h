@@ -442,4 +442,22 @@ int rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int32_t H,
 int rgbe_check_launch(cvvdp_handle* h);
 void launch_unpack_rgbe(const RgbeArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- display-model preview (preview.hip)
+// n_frames frames of one side -> a named colour space, packed (cvvdp_pixel_preview, include/cvvdp_hip.h).  The tiling is k_psnr_sse's.
+struct PreviewArgs {
+  PsnrArgs p;               // the source in both side slots (Y'CbCr: sf[0] / sf[1] = the test / reference frame stride), display model
+  int32_t side;             // which slot of p the kernel reads
+  int32_t target, format;   // CVVDP_PREVIEW_AS_IS / LINEAR / PQ; CVVDP_PREVIEW_F32 / RGBE / RGB48
+  float rows[9];
+  void* dst;
+  int64_t origin;           // y0 * sr + x0
+  int64_t sr, sf, sc;       // pixels between rows / frames of the canvas; F32: floats between channel planes
+};
+static_assert(sizeof(PreviewArgs) <= 4096, "kernel arguments of the preview kernel");
+// core.cpp: argument checks and kernel arguments of cvvdp_pixel_preview; the error of a launch
+int preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref, int32_t B,
+                    int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_preview_args* args, void* dst, size_t dst_bytes, PreviewArgs& a);
+int preview_check_launch(cvvdp_handle* h);
+void launch_preview(const PreviewArgs& a, hipStream_t s);
+
 }  // namespace cvvdp

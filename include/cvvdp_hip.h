@@ -394,6 +394,46 @@ const char* cvvdp_rgbe_strerror(int code);
 int cvvdp_unpack_rgbe(cvvdp_handle* h, const void* dev_rgbe, int32_t n_frames, int32_t H, int32_t W, float* dev_out, int64_t stride_c,
                       int64_t stride_f, void* stream);
 
+/* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
+ * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
+ * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
+ * model (display_model.py:333-365), then rows (3x3) . L with every product rounded and the three summed left to right
+ * (display_model.py:266-270), then for CVVDP_PREVIEW_PQ lin2pq (display_model.py:44-56).  1-channel content (C = 1) is not multiplied
+ * by rows: R = G = B = the emitted luminance, PQ-encoded under CVVDP_PREVIEW_PQ.
+ * Output pixel (x, y) of frame f goes to pixel index f * dst_stride_frame + (y0 + y) * dst_stride_row + (x0 + x) of dev_dst (strides
+ * in pixels), so that two calls can fill the halves of one side-by-side canvas:
+ *   CVVDP_PREVIEW_F32    fp32, channel c at float index + c * dst_stride_c: planes (dev_dst 4-byte aligned)
+ *   CVVDP_PREVIEW_RGBE   4 bytes per pixel R, G, B, E: the layout cvvdp_unpack_rgbe reads (dev_dst 4-byte aligned).  Ward's packing:
+ *                        channels below 0 count as 0 and channels above 255 * 2^119 (the largest RGBE value; +inf) as that; a pixel
+ *                        with a NaN channel or whose largest channel v is below 1e-32 is 0,0,0,0; otherwise v = m * 2^e with
+ *                        0.5 <= m < 1, scale = (m * 256) / v in fp32, code = min(trunc(channel * scale), 255), E = e + 128
+ *   CVVDP_PREVIEW_RGB48  three little-endian uint16 per pixel R, G, B: trunc(min(max(v, 0), 1) * 65535.0f), NaN as 0 -- what the
+ *                        reference pipes into ffmpeg as rgb48le (video_writer.py:70-72) (dev_dst 2-byte aligned)
+ * dst_bytes is the size of the canvas behind dev_dst; a call whose last pixel would lie outside it is refused.  Runs of pixels that lie
+ * in one row and start 16-byte aligned in the canvas are written with 16-byte stores, everything else element by element: the bytes
+ * do not depend on which.  No scratch, no reductions; needs no configured clip. */
+enum {
+  CVVDP_PREVIEW_AS_IS = 0,   /* the samples as they are (frames a source has already converted); not for Y'CbCr dtypes */
+  CVVDP_PREVIEW_LINEAR = 1,  /* rows . forward(V): fp32 XYZ_to_RGB709 @ rgb2xyz or XYZ_to_RGB2020 @ rgb2xyz, cd/m^2 */
+  CVVDP_PREVIEW_PQ = 2       /* lin2pq(rows . forward(V)), rows = fp32 XYZ_to_RGB2020 @ rgb2xyz: 'RGB2020pq' */
+};
+enum { CVVDP_PREVIEW_F32 = 0, CVVDP_PREVIEW_RGBE = 1, CVVDP_PREVIEW_RGB48 = 2 };
+typedef struct cvvdp_preview_args {
+  int32_t target;          /* CVVDP_PREVIEW_AS_IS / _LINEAR / _PQ */
+  int32_t out_format;      /* CVVDP_PREVIEW_F32 / _RGBE / _RGB48 */
+  float rows[9];           /* row-major; finite for _LINEAR and _PQ */
+  int32_t x0, y0;          /* origin of the frames in the canvas, >= 0 */
+  int32_t reserved;
+  int64_t dst_stride_row;  /* pixels, >= x0 + W */
+  int64_t dst_stride_frame;/* pixels */
+  int64_t dst_stride_c;    /* CVVDP_PREVIEW_F32: floats between channel planes */
+} cvvdp_preview_args;
+int cvvdp_pixel_preview(cvvdp_handle* h, const void* dev_src, int32_t dtype, const int64_t strides[5], const cvvdp_yuv_format* yuv,
+                        int32_t is_ref, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_preview_args* args,
+                        void* dev_dst, size_t dst_bytes, void* stream);
+/* sizeof(cvvdp_preview_args) as compiled. */
+int32_t cvvdp_preview_args_size(void);
+
 /* Sources that deliver temporally pre-filtered channels (vid_source.is_temporally_filtered, cvvdp_metric.py:470-488):
  * frames are fp32 [B, 4, n, H, W] in colour space 'DKLd65_trans' (Y-sustained, RG, YV, Y-transient; element strides in
  * B,C,F,H,W order) and go straight into the 8 level-0 planes (test channel c -> plane 2c, reference -> 2c+1), bypassing
