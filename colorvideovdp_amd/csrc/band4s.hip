@@ -6,15 +6,20 @@
 // block barriers and ~1150 issue cycles, and one other wave cannot cover it.  The two big pieces of per-lane state never meet:
 //   * FRONT waves (one per channel, waves 0..3): stream the level-l rows (hand-issued loads, the 8-row register ring), reduce row
 //     r+5 (horizontal 5-tap + the running vertical sums), store the completed coarse row as level l+1, roll the 3-row expand window,
-//     write the vertically expanded row r+1 into s_ve, hand the RAW row r+1 to the back through LDS (s_g), and -- one column per
-//     thread -- the luminance terms of row r+1 (1/L_T, 1/L_R, the CSF sensitivities of all channels).
-//   * BACK waves (one per channel, waves 4..7): horizontal expand + Weber contrast + min / difference of row r (from s_ve, s_g,
-//     s_lum, s_S), the horizontal 13-tap blur of the same row (s_m is written and read by the same wave: no block barrier), the
-//     13-row vertical blur window in registers, masking, soft clamp and pooling seven rows behind.
+//     expand row r+1 vertically, and -- one column per thread -- the luminance terms of row r+1 (1/L_T, 1/L_R, the CSF sensitivities
+//     of all channels).  What they hand to the back through LDS (s_g):
+//       - the plain kernels (LATE): the LAPLACIAN of row r+1, finished where its inputs are -- the raw row (the ring) and the lane's
+//         four vertically expanded coarse values are in registers, the neighbour lanes' coarse columns one DPP move away -- so only
+//         channel 0's vertically expanded row still goes to s_ve (the luminance terms read it);
+//       - _heat / _feat: the vertically expanded row r+1 (s_ve) and the RAW row r+1 (s_g).
+//   * BACK waves (one per channel, waves 4..7): Weber contrast + min / difference of row r from the Laplacian in s_g (_heat / _feat:
+//     the horizontal half of the expand from s_ve and the subtraction from the raw row first) and s_lum, s_S, the horizontal 13-tap
+//     blur of the same row (s_m is written and read by the same wave: no block barrier), the 13-row vertical blur window in
+//     registers, masking, soft clamp and pooling seven rows behind.
 // Each kind needs <= 128 VGPRs, so a CU holds two 8-wave blocks = four waves per SIMD, and -- waves being dealt to the SIMDs round
 // robin -- every SIMD gets the front and the back wave of one channel of each block: the work per SIMD is what it was, but a wave's
 // chain is half as long and three other waves stand by.  Same two barriers per row; per-row hand-offs are double-buffered by row
-// parity (s_ve, s_g).  LDS: 71.5 - 75.5 KB per block (k_band4f: 50) -- two blocks per CU fit the 160 KB (static_assert below).
+// parity (s_ve, s_g).  LDS: 68.8 - 75.5 KB per block (k_band4f: 50) -- two blocks per CU fit the 160 KB (static_assert below).
 //
 // The arithmetic is k_band4f<4, 0>'s, operation for operation (same FMA chains, same order): the two kernels' level-(l+1) planes are
 // bit-identical and their partial sums agree to the last bit -- they are two separately compiled kernels, and the compiler contracts a
@@ -64,6 +69,11 @@ __device__ __forceinline__ void s_for_seq(F&& f, std::integer_sequence<int, Us..
 #define CVVDP_BAND4S_RING 8         // rows of the front waves' register ring (STREAM LOADS)
 #endif
 
+// A/B switch (tools/build_variant.sh; same results): S_DIAG_LAP_BACK keeps the hand-off of _heat / _feat in the plain kernels too -- the
+// front hands the raw and the vertically expanded row over, the back waves finish the Laplacian (profiles/r08_ab_lap_handoff.txt)
+#if defined(S_DIAG_NO_SG) && !defined(S_DIAG_LAP_BACK)
+#error "S_DIAG_NO_SG drops the raw-row hand-off, which the plain kernels have only with -DS_DIAG_LAP_BACK"
+#endif
 // timing-only diagnostics (tools/build_variant.sh; results wrong by construction): S_DIAG_NOBAR drops the block barriers of the row loops
 #ifdef S_DIAG_NOBAR
 #define S_SYNC() __builtin_amdgcn_wave_barrier()
@@ -82,18 +92,25 @@ struct __attribute__((packed, aligned(4))) s_u4 { float x, y, z, w; };     // 16
 // it -- and function-local __shared__ arrays of two instantiations would be allocated twice)
 // LATE: the plain kernels pool row r-7 in PHASE 2 of row r's step (band4s_body, BACK: the row step's order).  The pooled row's Mq of all
 // four channels (s_q) and its |T'-R'| (s_d) must then outlive what phase 1 / phase 2 of the same step write: s_q has two buffers by row
-// parity and the lane-private ring of s_d an eighth row.  +7.9 KB: 75 312 bytes per block, two blocks per CU (160 KB) as before.
+// parity and the lane-private ring of s_d an eighth row (+7.9 KB).
+// LAP_FRONT: the plain kernels' front waves hand the finished Laplacian to the back (band4s_body, FRONT: coarse_finish), so s_ve keeps
+// only the two planes lum_prep reads (channel 0's Y, test and reference): -6.4 KB, 68 784 bytes per block; two blocks per CU (160 KB).
 template <bool HEAT, bool FEAT>
 struct S4Lds {
   static constexpr int NCH = 4, NP = 8;
   static constexpr bool LATE = !HEAT && !FEAT;
+#ifdef S_DIAG_LAP_BACK
+  static constexpr bool LAP_FRONT = false;
+#else
+  static constexpr bool LAP_FRONT = LATE;
+#endif
   static constexpr int NQ = LATE ? 2 : 1, ND = LATE ? S_R + 2 : S_R + 1;
   __attribute__((aligned(16))) float s_h[HEAT ? NCH : 1][HEAT ? 256 : 4];   // heat-map terms of the pooled row, per channel
   // FEAT: the column sums of D and D^2 live in LDS (lane-private: no barrier) -- with all 24 sums in registers the back waves spilled
   // eight constants and reloaded three of them per row from scratch (level 0 of 4K x 64: 10.5 ms against 7.2 of the plain kernel)
   __attribute__((aligned(16))) float s_fd[2][FEAT ? NCH : 1][FEAT ? 256 : 4];
-  __attribute__((aligned(16))) float2 s_ve[2][NP][S_VE / 2];
-  __attribute__((aligned(16))) float s_g[2][NP][256];             // raw level-l row handed from the front to the back (by row parity)
+  __attribute__((aligned(16))) float2 s_ve[2][LAP_FRONT ? 2 : NP][S_VE / 2];   // vertically expanded coarse row (by row parity)
+  __attribute__((aligned(16))) float s_g[2][NP][256];             // front -> back, by row parity: the level-l row's Laplacian (LAP_FRONT) / the raw row
   __attribute__((aligned(16))) float s_lum[2][256];               // 1/L_T, 1/L_R
   __attribute__((aligned(16))) float s_S[NCH][256];
   __attribute__((aligned(16))) float s_m[NCH][256];
@@ -111,8 +128,9 @@ static_assert(sizeof(S4Lds<false, false>) <= 80 * 1024 && sizeof(S4Lds<true, fal
 // kernel, and at levels 1 and 2 that launch took as long as all other strips together (profiles/r04_dev_notes.txt 10).
 template <bool HEAT, bool FEAT, bool EDGE>
 __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>& L, const int strip, const int seg, const int item) {
-  constexpr int NCH = 4, NP = 8;
+  constexpr int NCH = 4;
   constexpr bool LATE = S4Lds<HEAT, FEAT>::LATE;
+  constexpr bool LAP_FRONT = S4Lds<HEAT, FEAT>::LAP_FRONT;
   constexpr int ND = S4Lds<HEAT, FEAT>::ND;
   auto& s_h = L.s_h; auto& s_fd = L.s_fd; auto& s_ve = L.s_ve; auto& s_g = L.s_g; auto& s_lum = L.s_lum; auto& s_S = L.s_S;
   auto& s_m = L.s_m; auto& s_q = L.s_q; auto& s_d = L.s_d; auto& s_lut = L.s_lut;
@@ -142,7 +160,7 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
     const float l1 = a.lut[cc * CVVDP_CSF_NODES + min(k + 1, CVVDP_CSF_NODES - 1)] * kLog2_10 + fast_log2(a.sens_mul * a.ch_gain[cc] * a.band_mul);
     s_lut[cc][k] = make_float2(l0, l1 - l0);
   }
-  for (int i = t; i < 2 * NP * (S_VE / 2); i += 512) (&s_ve[0][0][0])[i] = make_float2(0.0f, 0.0f);
+  for (int i = t; i < (int)(sizeof(s_ve) / sizeof(float2)); i += 512) (&s_ve[0][0][0])[i] = make_float2(0.0f, 0.0f);
   __syncthreads();
 
 #ifndef S_DIAG_BACK_ONLY
@@ -174,8 +192,9 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
     float4 cA = make_float4(0, 0, 0, 0), cB = cA, cC = cA;          // coarse rows my-1, my, my+1 of this lane's two coarse columns: (T0, T1, R0, R1)
     float4 rP = cA, rQ = cA;                                        // partial sums of the two coarse rows under construction (older, younger)
 
-    // vertical expand of one fine row from the window -> s_ve[buf] (lpyr_dec.py:229-232); roll: a new coarse row enters first
-    auto coarse_finish = [&](int buf, auto odd_row, bool roll, float4 emitted) {
+    // vertical expand of one fine row from the window -> s_ve[buf] (lpyr_dec.py:229-232); roll: a new coarse row enters first.
+    // LAP_FRONT: and the rest of that row's Laplacian here, from its raw samples rawT / rawR -> s_g[buf]
+    auto coarse_finish = [&](int buf, auto odd_row, bool roll, float4 emitted, v4f rawT, v4f rawR) {
       if (roll) { cA = cB; cB = cC; cC = emitted; }
       const float m0[4] = {cA.x, cA.y, cA.z, cA.w}, m1[4] = {cB.x, cB.y, cB.z, cB.w}, m2[4] = {cC.x, cC.y, cC.z, cC.w};
       float o[4];
@@ -186,8 +205,29 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = expand_even(m0[i], m1[i], m2[i], e0, e1);
       }
-      s_ve[buf][2 * c][2 + j] = make_float2(o[0], o[1]);           // coarse columns cb+2j, cb+2j+1 of the test plane ...
-      s_ve[buf][2 * c + 1][2 + j] = make_float2(o[2], o[3]);       // ... and of the reference plane
+      if constexpr (LAP_FRONT) {
+        if (c == 0) {                                                // (scalar) lum_prep reads channel 0's Y and nothing else
+          s_ve[buf][0][2 + j] = make_float2(o[0], o[1]);
+          s_ve[buf][1][2 + j] = make_float2(o[2], o[3]);
+        }
+        // horizontal half of the expand for this lane's 4 columns (lpyr_dec.py:234-237; kernels.h expand_even / expand_odd in the order
+        // of the back waves' expand4) and the subtraction.  The coarse columns either side are the neighbour lanes' (all 64 lanes are
+        // active here): wave_shr:1 / wave_shl:1 with bound_ctrl hand lanes 0 and 63 a 0, which is what the never-written s_ve entries [1]
+        // and [66] give expand4 -- columns of the strip's halo, outside what the blur reads.  EDGE: the replicas of the coarse columns
+        // outside the image are in `emitted` already.  One plane at a time (both together: 128 VGPRs and two spills).
+        auto shr = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true)); };   // wave_shr:1
+        auto shl = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true)); };   // wave_shl:1
+        auto lap4 = [&](v4f raw, float B, float C) -> v4f {
+          const float A = shr(C), D = shl(B);
+          return v4f{raw.x - expand_even(A, B, C, e0, e1), raw.y - expand_odd(B, C, eo), raw.z - expand_even(B, C, D, e0, e1), raw.w - expand_odd(C, D, eo)};
+        };
+        *reinterpret_cast<v4f*>(&s_g[buf][2 * c][4 * j]) = lap4(rawT, o[0], o[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        *reinterpret_cast<v4f*>(&s_g[buf][2 * c + 1][4 * j]) = lap4(rawR, o[2], o[3]);
+      } else {
+        s_ve[buf][2 * c][2 + j] = make_float2(o[0], o[1]);           // coarse columns cb+2j, cb+2j+1 of the test plane ...
+        s_ve[buf][2 * c + 1][2 + j] = make_float2(o[2], o[3]);       // ... and of the reference plane
+      }
     };
 
     // One level-l row (four own samples + three neighbours per plane) through the horizontal pass, then into the running sums
@@ -380,9 +420,11 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
         const v4f vT = ld4(gT, ar), vR = ld4(gR, ar);
         const v2f lT = ld2(gT, ar), lR = ld2(gR, ar);
         const float rT = ld1(gT, ar), rR = ld1(gR, ar);
-        if (i == 4) {                                                 // raw row r_start goes straight to the back
-          *reinterpret_cast<v4f*>(&s_g[0][2 * c][4 * j]) = vT;
-          *reinterpret_cast<v4f*>(&s_g[0][2 * c + 1][4 * j]) = vR;
+        if constexpr (!LAP_FRONT) {
+          if (i == 4) {                                               // raw row r_start goes straight to the back
+            *reinterpret_cast<v4f*>(&s_g[0][2 * c][4 * j]) = vT;
+            *reinterpret_cast<v4f*>(&s_g[0][2 * c + 1][4 * j]) = vR;
+          }
         }
         if (i > 4) { ringT[i - 4] = vT; ringR[i - 4] = vR; }           // rows r_start+1 .. r_start+4 in slots 1 .. 4 (the ring holds the rows as loaded)
         if (i & 1) {
@@ -404,7 +446,10 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
       load_nb(std::integral_constant<int, 0>{}, rowc(r_start + 6));
       S_LOAD4(ringT[0], goff, gT, rowc(r_start + S_RING));
       S_LOAD4(ringR[0], goff, gR, rowc(r_start + S_RING));
-      coarse_finish(0, std::false_type{}, false, cC);                 // vertical expand of row r_start (even)
+      // vertical expand of row r_start (even).  LAP_FRONT: its raw samples are loaded again -- kept live across the priming loop they
+      // cost three spills
+      if constexpr (LAP_FRONT) coarse_finish(0, std::false_type{}, false, cC, ld4(gT, r_start), ld4(gR, r_start));
+      else coarse_finish(0, std::false_type{}, false, cC, v4f{}, v4f{});
     }
     __syncthreads();
     lum_prep(0);
@@ -420,10 +465,13 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
       // ================= phase 1: level-l row r+5 into the reduce; an even row completes a coarse row, which rolls the window for row r+1
       float4 emitted = cC;
       consume(r + 5, std::integral_constant<bool, !ODD>{}, ringT[S5], ringR[S5], nbLT[P5], nbRT[P5], nbLR[P5], nbRR[P5], emitted);
-      coarse_finish(ODD ? 0 : 1, std::integral_constant<bool, !ODD>{}, ODD, emitted);   // vertical expand of row r+1
+      // vertical expand of row r+1; its raw samples arrived long ago
+      coarse_finish(ODD ? 0 : 1, std::integral_constant<bool, !ODD>{}, ODD, emitted, ringT[S1], ringR[S1]);
 #ifndef S_DIAG_NO_SG
-      *reinterpret_cast<v4f*>(&s_g[ODD ? 0 : 1][2 * c][4 * j]) = ringT[S1];             // raw row r+1 for the back (arrived long ago)
-      *reinterpret_cast<v4f*>(&s_g[ODD ? 0 : 1][2 * c + 1][4 * j]) = ringR[S1];
+      if constexpr (!LAP_FRONT) {
+        *reinterpret_cast<v4f*>(&s_g[ODD ? 0 : 1][2 * c][4 * j]) = ringT[S1];           // raw row r+1 for the back
+        *reinterpret_cast<v4f*>(&s_g[ODD ? 0 : 1][2 * c + 1][4 * j]) = ringR[S1];
+      }
 #endif
       S_SYNC();
       // ================= phase 2
@@ -664,9 +712,11 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
       }
       const bool feat_row = FEAT && r >= ys && r < ye;  // (scalar) row r belongs to this segment: its |T'|, |R'| are counted
       if (in_img) {                                     // (EDGE == 0: every lane)
-        float exT[4], exR[4];
-        expand4(s_ve[ODD][2 * c], exT);
-        expand4(s_ve[ODD][2 * c + 1], exR);
+        float exT[4] = {0.0f, 0.0f, 0.0f, 0.0f}, exR[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (!LAP_FRONT) {
+          expand4(s_ve[ODD][2 * c], exT);
+          expand4(s_ve[ODD][2 * c + 1], exR);
+        }
         const sf4 rLt = s_lds_read4(&s_lum[0][4 * j]), rLr = s_lds_read4(&s_lum[1][4 * j]);
         const sf4 Sv = s_lds_read4(&s_S[c][4 * j]);
         const sf4 gt = s_lds_read4(&s_g[ODD][2 * c][4 * j]), gr = s_lds_read4(&s_g[ODD][2 * c + 1][4 * j]);
@@ -687,8 +737,9 @@ __device__ __forceinline__ void band4s_body(const BandArgs& a, S4Lds<HEAT, FEAT>
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float S = Sv.v[i];
-          const float ct = fminf((gt.v[i] - exT[i]) * rLt.v[i], 1000.0f);            // lpyr_dec.py:402 (band gain :66 is in S)
-          const float cr = fminf((gr.v[i] - exR[i]) * rLr.v[i], 1000.0f);
+          // lpyr_dec.py:402 (band gain :66 is in S).  LAP_FRONT: s_g holds the Laplacian, not the raw row
+          const float ct = fminf((LAP_FRONT ? gt.v[i] : gt.v[i] - exT[i]) * rLt.v[i], 1000.0f);
+          const float cr = fminf((LAP_FRONT ? gr.v[i] : gr.v[i] - exR[i]) * rLr.v[i], 1000.0f);
           if constexpr (FEAT) {
             const float at = fabsf(ct) * S, ar = fabsf(cr) * S;                    // |T'|, |R'| (the channel gain inside S is divided out by k_feature_finish)
             m[i] = fminf(at, ar);                                                  // = min(|ct|,|cr|)*S bit for bit (rounding is monotone)
@@ -880,7 +931,7 @@ int tu_flags_band4s() {
   f |= CVVDP_BUILD_SAFE_LOADS;
 #endif
 #if defined(S_DIAG_NOBAR) || defined(S_DIAG_BACK_ONLY) || defined(S_DIAG_FRONT_ONLY) || defined(S_DIAG_NO_STORE) || defined(S_DIAG_PLAIN_STORE) || \
-    defined(S_DIAG_NO_NB) || defined(S_DIAG_NO_SG) || defined(S_DIAG_EDGE_RING) || defined(S_DIAG_NO_LUM) || defined(S_DIAG_VB4) || defined(S_PRIO_FRONT) || defined(S_PRIO_BACK) || CVVDP_BAND4S_RING != 8
+    defined(S_DIAG_LAP_BACK) || defined(S_DIAG_NO_NB) || defined(S_DIAG_NO_SG) || defined(S_DIAG_EDGE_RING) || defined(S_DIAG_NO_LUM) || defined(S_DIAG_VB4) || defined(S_PRIO_FRONT) || defined(S_PRIO_BACK) || CVVDP_BAND4S_RING != 8
   f |= CVVDP_BUILD_DIAG;
 #endif
   return f;
