@@ -114,6 +114,10 @@ PREVIEW_F32, PREVIEW_RGBE, PREVIEW_RGB48 = range(3)       # CVVDP_PREVIEW_* outp
 PREVIEW_PIXEL_BYTES = {PREVIEW_F32: 12, PREVIEW_RGBE: 4, PREVIEW_RGB48: 6}
 
 
+DUMP_TEMPORAL, DUMP_LPYR, DUMP_DIFF = range(3)              # CVVDP_DUMP_*
+DUMP = {"temporal": DUMP_TEMPORAL, "lpyr": DUMP_LPYR, "difference": DUMP_DIFF}
+
+
 class PreviewArgs(C.Structure):
     _fields_ = [
         ("target", C.c_int32), ("out_format", C.c_int32),
@@ -173,6 +177,8 @@ SYMBOLS = {
     "cvvdp_preview_args_size": (C.c_int32, []),
     "cvvdp_pixel_preview": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(PreviewArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_dump_canvas_size": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cvvdp_dump_channels": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_process_block_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.c_int32, C.c_int32, C.c_void_p]),
     "cvvdp_get_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

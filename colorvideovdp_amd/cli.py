@@ -12,7 +12,11 @@ JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpe
   * the heat map of a VIDEO is streamed block by block: into `<base>_heatmap.mp4` through an ffmpeg pipe (the reference's
     file and codec settings) where an `ffmpeg` executable exists, otherwise into a numbered PNG sequence
     `<base>_heatmap_%05d.png` (`ffmpeg -i <base>_heatmap_%05d.png <base>_heatmap.mp4` converts it); an image gives `<base>_heatmap.png`;
-  * --device must be a cuda device; --temp-padding 'valid', --dump-channels, the cvvdp-ml heads and the OpenEXR previews
+  * --dump-channels temporal lpyr difference writes the reference's debugging pictures (pycvvdp/dump_channels.py) into --output-dir:
+    temp_channels.mp4, lpyr.mp4 and diff.mp4 for a video through an ffmpeg pipe where an `ffmpeg` executable exists, otherwise
+    `temp_channels_%05d.png` etc. with a warning; temp_channels.png, lpyr.png and diff.png for an image.  The pictures are packed on the
+    GPU (dump_channels.py); with them the core scores on its unfused route, so the JOD printed equals the plain one to rounding;
+  * --device must be a cuda device; --temp-padding 'valid', the cvvdp-ml heads and the OpenEXR previews
     (dm-preview-exr, dm-preview-exr-sbs: dm-preview-hdr and dm-preview-hdr-sbs write the same values as Radiance .hdr) are not available; --full-screen-resize works for .yuv clips (as in the
     reference it is not implemented for images);
   * --temp-resample [X] scores .yuv clips whose file names carry different frame rates (a 30 fps encode against its 60 fps source) at
@@ -35,6 +39,7 @@ import numpy as np
 import torch
 
 from . import heatmap_writers
+from .dump_channels import DumpChannels
 from .cvvdp_metric import cvvdp
 from . import psnr_metric  # noqa: F401  (registers psnr_rgb, pu_psnr_y, pu_psnr_rgb2020)
 from . import ssim_metric  # noqa: F401  (registers ssim_metric)
@@ -89,7 +94,10 @@ _OPTIONS = (
     (("--temp-resample",), dict(type=float, nargs="?", default=-1, const=0,
                                 help="score .yuv clips of different frame rates at a common rate (frames repeated); optional value = the highest such rate (default 166)")),
     (("-i", "--interactive"), dict(action="store_true", default=False, help="one command line per line of standard input")),
-    (("--dump-channels",), dict(nargs="+", choices=["temporal", "lpyr", "difference"], default=None, help=_NA)),
+    (("--dump-channels",), dict(nargs="+", choices=["temporal", "lpyr", "difference"], default=None,
+                                help="write the temporal channels, the contrast pyramid and / or the per-band differences as pictures into --output-dir "
+                                     "(temp_channels, lpyr, diff: .mp4 for a video, .png for an image).  With it the JOD printed is that of the core's "
+                                     "unfused route (fuse_mode = 2), equal to the plain one to rounding")),
 )
 
 
@@ -145,9 +153,6 @@ def run_on_args(args):
         logging.error("Paths to both test and reference content needs to be specified.")
         return
     frame_range = parse_frame_range(args.frames)
-    for opt, what in ((args.dump_channels, "--dump-channels"),):
-        if opt is not None:
-            raise vq_exception(f"{what} is not available in the MI355X build")
     if args.temp_resample >= 0:
         # refused before any file or device is touched: what the resampling source does not read
         for f in (args.test or []) + (args.ref or []):
@@ -188,8 +193,17 @@ def run_on_args(args):
         display_geometry = vvdp_display_geometry.load(args.display, config_paths=args.config_paths)
     else:
         display_geometry = vvdp_display_geometry([1024, 1024], ppd=args.pix_per_deg)
+    dump_channels = None
+    if args.dump_channels:
+        # (before anything is created: opening the dump's writers replaces the pictures of an earlier run)
+        for f in args.test + args.ref:
+            if "%" not in f and not os.path.isfile(f):
+                raise vq_exception(f"File not found: '{f}'")
     out_dir = "." if args.output_dir is None else args.output_dir
     os.makedirs(out_dir, exist_ok=True)
+    if args.dump_channels:                                                     # run_cvvdp.py:234-237
+        dump_channels = DumpChannels(dump_temp_ch=("temporal" in args.dump_channels), dump_lpyr=("lpyr" in args.dump_channels),
+                                     dump_diff=("difference" in args.dump_channels), output_dir=args.output_dir)
 
     metrics = []
     for mm in args.metric:
@@ -197,7 +211,8 @@ def run_on_args(args):
             raise RuntimeError(f"Unknown metric {mm}")
         fv = vq_metric_dict[mm](**metric_arguments(vq_metric_dict[mm], display_photometry=display_photometry, display_geometry=display_geometry,
                                                    device=device, heatmap=args.heatmap, temp_padding=args.temp_padding,
-                                                   config_paths=args.config_paths, gpu_mem=args.gpu_mem, quiet=args.quiet, verbose=args.verbose))
+                                                   config_paths=args.config_paths, gpu_mem=args.gpu_mem, quiet=args.quiet, verbose=args.verbose,
+                                                   dump_channels=dump_channels))
         fv.train(False)
         metrics.append(fv)
         info = fv.get_info_string()
@@ -260,6 +275,8 @@ def run_on_args(args):
     finally:
         if res_fh is not None:
             res_fh.close()
+        if dump_channels is not None:
+            dump_channels.close()
 
 
 def main(argv=None):

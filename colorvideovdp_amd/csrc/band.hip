@@ -17,6 +17,7 @@
 // Out-of-image taps of the blur use reflect padding (torchvision GaussianBlur): the halo is evaluated
 // at the reflected coordinate, so no separate padding pass exists.
 #include "kernels.h"
+#include "band_dev.h"
 
 namespace cvvdp {
 
@@ -83,18 +84,12 @@ __global__ __launch_bounds__(BT) void k_band(BandArgs a) {
     const int rr = reflect_idx(r, H);
     // ---- 1. vertical half of the expand (lpyr_dec.py:229-232) for the strip's coarse columns
     {
-      const int my = rr >> 1;
-      const int ya = max(my - 1, 0), yb = min(my + 1, Hc - 1);
+      int my, ya, yb;
+      expand_rows(rr, Hc, my, ya, yb);
       const bool odd = rr & 1;
       // threads 0..127 take planes 0,2,4,.. and threads 128..255 planes 1,3,5,..; coarse column = t & 127
       for (int ci = t & 127; ci < n_cx; ci += 128) {
-        for (int p = t >> 7; p < NP; p += 2) {
-          const float* cp = gc + p * gcps + (cx_lo + ci);
-          float v;
-          if (odd) v = expand_odd(cp[(int64_t)my * Wc], cp[(int64_t)yb * Wc], eo);
-          else v = expand_even(cp[(int64_t)ya * Wc], cp[(int64_t)my * Wc], cp[(int64_t)yb * Wc], e0, e1);
-          s_ve[p][ci] = v;
-        }
+        for (int p = t >> 7; p < NP; p += 2) s_ve[p][ci] = expand_col(gc + p * gcps + (cx_lo + ci), Wc, odd, my, ya, yb, e0, e1, eo);
       }
     }
     __syncthreads();
@@ -107,10 +102,10 @@ __global__ __launch_bounds__(BT) void k_band(BandArgs a) {
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         gv[p] = g[p * gps + (int64_t)rr * W + xx];
-        if (xx & 1) ex[p] = expand_odd(s_ve[p][cb], s_ve[p][cc], eo);               // lpyr_dec.py:234-237
+        if (xx & 1) ex[p] = expand_odd(s_ve[p][cb], s_ve[p][cc], eo);               // lpyr_dec.py:234-237 (expand_row, spelt out: the branch stays outside the taps)
         else ex[p] = expand_even(s_ve[p][ca], s_ve[p][cb], s_ve[p][cc], e0, e1);
       }
-      const float Lt = fmaxf(ex[0], 0.01f), Lr = fmaxf(ex[1], 0.01f);     // lpyr_dec.py:394
+      const float Lt = bkg_lum(ex[0]), Lr = bkg_lum(ex[1]);               // lpyr_dec.py:394
       const float rLt = fast_rcp(Lt), rLr = fast_rcp(Lr);
       const float logL = fast_log2(Lr) * kLog10_2;                        // lpyr_dec.py:408, query = reference plane
       float ind = (logL - a.logL_first) * ind_scale;                       // interp.py:93
@@ -122,8 +117,8 @@ __global__ __launch_bounds__(BT) void k_band(BandArgs a) {
       for (int c = 0; c < NCH; ++c) {
         const float l0 = s_lut[c * CVVDP_CSF_NODES + i0], l1 = s_lut[c * CVVDP_CSF_NODES + i1];
         const float S = fast_exp2(l0 + (l1 - l0) * fr) * a.ch_gain[c];      // csf.py:49, cvvdp_metric.py:709,:836
-        const float ct = fminf((gv[2 * c] - ex[2 * c]) * rLt, 1000.0f) * a.band_mul;       // lpyr_dec.py:402, :66
-        const float cr = fminf((gv[2 * c + 1] - ex[2 * c + 1]) * rLr, 1000.0f) * a.band_mul;
+        const float ct = weber_contrast(gv[2 * c], ex[2 * c], rLt) * a.band_mul;           // lpyr_dec.py:402, :66
+        const float cr = weber_contrast(gv[2 * c + 1], ex[2 * c + 1], rLr) * a.band_mul;
         const float Tp = ct * S, Rp = cr * S;
         m[c] = fminf(fabsf(Tp), fabsf(Rp));                                 // :845
         d[c] = fabsf(Tp - Rp);
@@ -243,16 +238,6 @@ void launch_band(const BandArgs& a, bool blur, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- baseband + finalize
-__device__ __forceinline__ float block_sum(float v, float* s_tmp) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int t = threadIdx.x;
-  __syncthreads();
-  if ((t & 63) == 0) s_tmp[t >> 6] = v;
-  __syncthreads();
-  return s_tmp[0] + s_tmp[1] + s_tmp[2] + s_tmp[3];
-}
-
 // Baseband (lpyr_dec.py:378-384, cvvdp_metric.py:711-712): L_bkg is the per-frame spatial mean of the
 // clamped Y planes, D = |T-R|*S without masking.  One block per item; the band is at most a few
 // hundred pixels.
@@ -262,13 +247,9 @@ __global__ __launch_bounds__(256) void k_baseband(BaseArgs a) {
   const int P = a.H * a.W;
   const int64_t ps = (int64_t)a.items_cap * P;
   const float* g = a.g + (int64_t)item * P;
-  float st = 0.0f, sr = 0.0f;
-  for (int i = t; i < P; i += 256) {
-    st += fmaxf(g[i], 0.01f);
-    sr += fmaxf(g[ps + i], 0.01f);
-  }
-  const float Lt = block_sum(st, s_tmp) / (float)P;
-  const float Lr = block_sum(sr, s_tmp) / (float)P;
+  float Lb[2];
+  base_bkg_mean<2>(g, ps, P, s_tmp, Lb);
+  const float Lt = Lb[0], Lr = Lb[1];
   const float logL = log10f(Lr);
   float ind = (logL - a.logL_first) / (a.logL_last - a.logL_first) * (float)(CVVDP_CSF_NODES - 1);
   ind = fminf(fmaxf(ind, 0.0f), (float)(CVVDP_CSF_NODES - 1));
@@ -285,8 +266,8 @@ __global__ __launch_bounds__(256) void k_baseband(BaseArgs a) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if (c < a.nch) {
-        const float ct = fminf(g[(2 * c) * ps + i] / Lt, 1000.0f);
-        const float cr = fminf(g[(2 * c + 1) * ps + i] / Lr, 1000.0f);
+        const float ct = base_contrast(g[(2 * c) * ps + i], Lt);
+        const float cr = base_contrast(g[(2 * c + 1) * ps + i], Lr);
         D[c] = fabsf(ct - cr) * S[c];
         if (a.fdump) {
           a.fdump[(int64_t)c * ps + (int64_t)item * P + i] = fabsf(ct) * S[c];

@@ -460,4 +460,64 @@ int preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64
 int preview_check_launch(cvvdp_handle* h);
 void launch_preview(const PreviewArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- --dump-channels mosaics (dump.hip)
+// The reference's debugging pictures (pycvvdp/dump_channels.py) packed as uint8 RGB, interleaved, straight into a canvas of n frames.
+struct DumpCanvas {
+  uint8_t* dst;             // 4-byte aligned
+  int64_t row_px, frame_px; // pixels between rows / frames of the canvas
+};
+struct DumpMaxArgs {        // max_V: the largest linear RGB value of the Y-sustained plane of one frame
+  const float* y;
+  int32_t P;
+  uint32_t* maxv;           // bit pattern of a float >= 0, zeroed before the launch
+};
+struct DumpTemporalArgs {
+  const float* g;           // plane 0 (test Y-sustained) of the first dumped frame at level 0
+  int64_t gps, gfs;         // floats between planes / dumped frames
+  int32_t H, W, n_frames, is_video;
+  const float* maxv;
+  DumpCanvas cv;
+};
+struct DumpQuads {          // the up to four quadrants of a band's launch: which plane, and where its band starts in the canvas
+  int32_t n;
+  int32_t plane[4], x0[4], y0[4];
+};
+struct DumpLpyrArgs {
+  const float* g;           // plane 0 of the first dumped frame at this level
+  const float* gc;          // ... at the next level (not read by the baseband)
+  int64_t gps, gcps, gfs, gcfs;
+  int32_t H, W, Hc, Wc, n_frames;
+  float kx[3];              // expand taps (BandArgs.kx)
+  float band_mul;           // lpyr_dec.py:60-66
+  DumpQuads q;
+  DumpCanvas cv;
+};
+struct DumpDiffArgs {
+  const float* d;           // D of channel 0 of the first dumped frame at this level (CVVDP_BUF_DDUMP)
+  int64_t dps, dfs;         // floats between channels / dumped frames
+  int32_t H, W, n_frames;
+  float w[4];               // per_ch_w * t_int of the quadrant's channel (cvvdp_metric.py:739-741)
+  DumpQuads q;              // plane = D channel
+  DumpCanvas cv;
+};
+struct DumpPlan {           // everything cvvdp_dump_channels launches, filled by core.cpp
+  int32_t which, n_levels;
+  int32_t clear;            // 0..255: the byte the canvas is cleared with first; -1: every byte is written by the kernels
+  size_t clear_bytes;
+  int32_t need_max;         // temporal: this call starts at the clip's first frame and takes max_V from it
+  DumpMaxArgs mx;
+  DumpTemporalArgs t;
+  DumpLpyrArgs lp[CVVDP_MAX_LEVELS];
+  DumpDiffArgs df[CVVDP_MAX_LEVELS];
+};
+// core.cpp: argument checks and kernel arguments of cvvdp_dump_channels / cvvdp_dump_canvas_size; the error of a launch
+int dump_canvas(const cvvdp_handle* h, int32_t which, int32_t* height, int32_t* width);
+int dump_prepare(cvvdp_handle* h, int32_t which, int32_t frame0, int32_t n_frames, void* dst, size_t dst_bytes, DumpPlan& plan);
+int dump_check_launch(cvvdp_handle* h);
+int dump_hip_error(cvvdp_handle* h, const char* what, hipError_t e);
+void launch_dump_max(const DumpMaxArgs& a, hipStream_t s);
+void launch_dump_temporal(const DumpTemporalArgs& a, hipStream_t s);
+void launch_dump_lpyr(const DumpLpyrArgs& a, bool baseband, hipStream_t s);
+void launch_dump_diff(const DumpDiffArgs& a, hipStream_t s);
+
 }  // namespace cvvdp

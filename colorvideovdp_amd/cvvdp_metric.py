@@ -206,6 +206,63 @@ class _HeatmapOut:
             self.copy_stream.synchronize()   # the heat map is host data: it must be complete when predict() returns
 
 
+class _DumpOut:
+    """Where the --dump-channels pictures of one _score_range call go (colorvideovdp_amd/dump_channels.py): `fetch(n)` has the core pack
+    the enabled pictures of the n frames scored last and starts their copy into one of two page-locked staging buffers, then hands the
+    frames of the block BEFORE to the writers, in order, while that copy and the next block's kernels run; `finish()` delivers the last
+    block.  The staging buffers stay on the metric (`_dump_stage`) between calls."""
+
+    def __init__(self, m, dc, stream):
+        self.m, self.dc, self.stream = m, dc, stream
+        self.names = dc.enabled()
+        self.sizes = {}
+        lib = _capi.lib()
+        for k in self.names:
+            h, w = ctypes.c_int32(), ctypes.c_int32()
+            _capi.check(m._handle, lib.cvvdp_dump_canvas_size(m._handle, _capi.DUMP[k], ctypes.byref(h), ctypes.byref(w)), "cvvdp_dump_canvas_size")
+            self.sizes[k] = (h.value, w.value)
+        self.pending, self.slot = None, 0
+
+    def fetch(self, n):
+        m, lib = self.m, _capi.lib()
+        packed = []
+        for k in self.names:
+            h, w = self.sizes[k]
+            buf = torch.empty((n, h, w, 3), dtype=torch.uint8, device=m.device)
+            _capi.check(m._handle, lib.cvvdp_dump_channels(m._handle, _capi.DUMP[k], 0, n, buf.data_ptr(), buf.numel(), self.stream), "cvvdp_dump_channels")
+            packed.append((k, buf))
+        need = sum(buf.numel() for _, buf in packed)
+        stage = getattr(m, "_dump_stage", None)
+        if stage is None or stage[0].numel() < need:
+            m._dump_stage = None                                                                            # (unpin the old pair first)
+            self._deliver()
+            stage = m._dump_stage = [torch.empty(need, dtype=torch.uint8, device="cpu", pin_memory=True) for _ in range(2)]
+        views, off = [], 0
+        for k, buf in packed:
+            view = stage[self.slot][off:off + buf.numel()].view(buf.shape)
+            view.copy_(buf, non_blocking=True)               # on the compute stream, behind the packers: stream order keeps `buf` alive
+            views.append((k, view))
+            off += buf.numel()
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(m.device))
+        self.slot ^= 1
+        self._deliver()                                      # the block before: its buffer is the one the NEXT fetch writes
+        self.pending = (ev, views)
+
+    def _deliver(self):
+        if self.pending is None:
+            return
+        (ev, views), self.pending = self.pending, None
+        ev.synchronize()
+        for k, view in views:
+            w, a = self.dc.writer(k), view.numpy()
+            for i in range(a.shape[0]):
+                w.write_frame_rgb(a[i])
+
+    def finish(self):
+        self._deliver()
+
+
 class cvvdp(vq_metric):
     def __init__(self, display_name="standard_4k", display_photometry=None, display_geometry=None, config_paths=[],
                  heatmap=None, quiet=False, device=None, temp_padding="replicate", use_checkpoints=False, dump_channels=None,
@@ -219,9 +276,12 @@ class cvvdp(vq_metric):
         self.training_mode = False
         assert heatmap in ["threshold", "supra-threshold", "raw", "none", None], "Unknown heatmap type"
         self.do_heatmap = (self.heatmap is not None) and (self.heatmap != "none")
-        if dump_channels:
-            raise vq_exception("dump_channels is a debugging aid of the reference implementation and is not supported")
-        self.dump_channels = None
+        # colorvideovdp_amd.dump_channels.DumpChannels (the reference's pycvvdp.dump_channels.DumpChannels): temporal channels, contrast
+        # pyramid and differences as pictures.  The core then keeps its per-pixel planes (cvvdp_clip.debug_dump) and scores on the unfused
+        # route: the JOD is that of fuse_mode = 2, equal to the plain one to rounding
+        if dump_channels is not None and not all(hasattr(dump_channels, a) for a in ("open", "enabled", "writer")):
+            raise vq_exception("dump_channels must be a colorvideovdp_amd.dump_channels.DumpChannels")
+        self.dump_channels = dump_channels
         _capi.lib()  # fail loudly (ImportError) if the HIP library is missing
         if device is None:
             self.device = torch.device("cuda")
@@ -521,6 +581,8 @@ class cvvdp(vq_metric):
         [B, F, H', W', channels, 6]; heatmap is None (the ML metrics produce none, :117-118)."""
         if self.do_heatmap:
             raise vq_exception("Currently cvvdp-ml metrics do not produce heatmaps")
+        if self.dump_channels is not None:
+            raise vq_exception("dump_channels is not available with extract_features (the feature kernels keep no per-pixel planes)")
         height, width, N_frames = vid_source.get_video_size()
         self._feature_out = []
         try:
@@ -543,6 +605,8 @@ class cvvdp(vq_metric):
         group = None
         sharded = False
         if self._shard is not None and not is_image and torch.distributed.is_available() and torch.distributed.is_initialized():
+            if self.dump_channels is not None:
+                raise vq_exception("dump_channels is not available with frame sharding: every rank would write the same files")
             group = None if self._shard == "world" else self._shard
             rank, world = torch.distributed.get_rank(group), torch.distributed.get_world_size(group)
             first, count = plan_frame_shard(N_frames, rank, world)
@@ -594,6 +658,9 @@ class cvvdp(vq_metric):
             if self.gpu_mem is not None:
                 budget = min(budget, self.gpu_mem * 1e9)
             per_frame = pix * batch * (2 * nch * 4 * 1.34) + (pix * 16 if self.do_heatmap else 0)
+            if self.dump_channels is not None:
+                # the per-pixel D of every band (4 planes with their pyramid) and the 8-bit canvases: 2H x 2W, and two of about 2H x 3W
+                per_frame += pix * batch * 4 * 4 * 1.34 + pix * 3 * (4 + 6 + 6) * 1.1
             fixed = pix * batch * 24 * (fl - 1)
             nb = int((budget - fixed) // per_frame)
             # heat maps leave the GPU over PCIe (2-6 B/pixel): 16-frame blocks let the copy of a block overlap the
@@ -625,6 +692,11 @@ class cvvdp(vq_metric):
                 nb = nb_long if nb_long > piece else min(nb, 16)
             else:
                 nb = min(nb, 16 if self.do_heatmap else (_capi.MAX_WINDOW - fl + 1 if long_ok else 64))
+            if self.dump_channels is not None:
+                # the canvases of a block wait in one of two page-locked staging buffers for their writers: at most 16 frames and about
+                # 256 MiB each (a 4K frame's three canvases are 400 MB: such clips are dumped frame by frame)
+                canvases = pix * sum({"temporal": 12.0, "lpyr": 18.2, "difference": 18.2}[k] for k in self.dump_channels.enabled())
+                nb = min(nb, 16, max(1, int((256 << 20) // max(canvases, 1.0))))
             if host_resident and n_frames > 24:
                 nb = min(nb, 16)   # the upload of block k+1 (side stream, worker thread) hides behind the kernels of block k
         return max(1, min(nb, n_frames, _capi.MAX_WINDOW - fl + 1))
@@ -736,7 +808,7 @@ class cvvdp(vq_metric):
         calls on clips of the same shape reuse it, so the first kernel is not held back by ~0.4 ms of host set-up."""
         height, width, is_image, prefiltered = rt.height, rt.width, rt.is_image, rt.prefiltered
         key = (height, width, rt.n_total, first, count, rt.B, rt.C, is_image, None if is_image else float(vs.get_frames_per_second()), self.heatmap,
-               bool(self.debug_dump), int(self.fuse_mode), int(self.band_layout), self.score_frames, self._sink_on_device, self.block_frames, self.gpu_mem, float(self.pix_per_deg), self._cfg_version, prefiltered, getattr(self, "_feature_out", None) is not None,
+               bool(self.debug_dump or self.dump_channels is not None), int(self.fuse_mode), int(self.band_layout), self.score_frames, self._sink_on_device, self.block_frames, self.gpu_mem, float(self.pix_per_deg), self._cfg_version, prefiltered, getattr(self, "_feature_out", None) is not None,
                self._host_resident(vs))
         cached = getattr(self, "_clip_cache", None)
         if cached is not None and cached[0] == key:
@@ -750,7 +822,7 @@ class cvvdp(vq_metric):
         clip.first_frame = first
         clip.total_frames = rt.n_total
         clip.heatmap = _capi.HEATMAP[self.heatmap]
-        clip.debug_dump = int(self.debug_dump)
+        clip.debug_dump = int(bool(self.debug_dump or self.dump_channels is not None))
         clip.fuse_mode = int(self.fuse_mode)
         clip.band_layout = int(self.band_layout)
         clip.feature_size = int(math.ceil(self.pix_per_deg)) if getattr(self, "_feature_out", None) is not None else 0   # cvvdp_ml_metric.py:353
@@ -773,7 +845,7 @@ class cvvdp(vq_metric):
             self.last_block_frames = nb
             # heat-map clips resident in HBM are scored in pieces of a long temporal block (see _pick_block_frames)
             piece = self._piece_frames()
-            if self.do_heatmap and clip.raw_halo and not prefiltered and not self.debug_dump and nb > piece:
+            if self.do_heatmap and clip.raw_halo and not prefiltered and not clip.debug_dump and nb > piece:
                 clip.defer_bands, clip.score_frames = 1, piece
         rows = np.zeros((_capi.MAX_LEVELS, 4, _capi.CSF_NODES), dtype=f32)
         for bb in range(rt.L):
@@ -823,6 +895,8 @@ class cvvdp(vq_metric):
         """Heat map and features of the n frames scored last, which start at frame `ff` of the range."""
         if out is not None and heatmap:
             out.fetch(ff, n)
+        if getattr(self, "_dump_out", None) is not None:
+            self._dump_out.fetch(n)
         if getattr(self, "_feature_out", None) is not None:
             for bb in range(rt.L):
                 dst = self._feature_out[bb][ff * rt.B:(ff + n) * rt.B]
@@ -911,7 +985,6 @@ class cvvdp(vq_metric):
 
     def _score_range(self, vs, first, count, heatmap_sink=None):
         """Q_per_ch [B, C, count, bands] (device tensor) of frames [first, first+count), the heat map if it is kept whole, rho_band."""
-        lib = _capi.lib()
         self._sink_on_device = bool(getattr(heatmap_sink, "wants_device", False))
         rt = self._route(vs, first)
         clip, fl, _F = self._plan_clip(vs, rt, first, count)
@@ -922,6 +995,19 @@ class cvvdp(vq_metric):
             piece = 1 if rt.is_image else (clip.score_frames if clip.defer_bands else clip.block_frames)
             out = _HeatmapOut(self, heatmap_sink, first, count, rt.height, rt.width, piece, stream)
         self._alloc_features(rt, clip, count)
+        self._dump_out = None
+        if self.dump_channels is not None:
+            if getattr(self, "_feature_out", None) is not None:
+                raise vq_exception("dump_channels is not available with extract_features (the feature kernels keep no per-pixel planes)")
+            self.dump_channels.open(0 if rt.is_image else vs.get_frames_per_second())        # cvvdp_metric.py:365-366
+            self._dump_out = _DumpOut(self, self.dump_channels, stream)
+        try:
+            return self._score_planned(vs, rt, clip, fl, first, count, out, stream)
+        finally:
+            self._dump_out = None
+
+    def _score_planned(self, vs, rt, clip, fl, first, count, out, stream):
+        lib = _capi.lib()
         if rt.is_image:
             st, sr = self._strides(rt.probe_t, rt.probe_r)
             rc = lib.cvvdp_put_image(self._handle, rt.probe_t.data_ptr(), rt.probe_r.data_ptr(), rt.code, st, sr, stream)
@@ -945,6 +1031,8 @@ class cvvdp(vq_metric):
         self._seq = None
         if out is not None:
             out.finish()
+        if self._dump_out is not None:
+            self._dump_out.finish()
         return Q, (out.heatmap if out is not None else None), rt.rho_band
 
     # ------------------------------------------------------------------ pooling, info, outputs

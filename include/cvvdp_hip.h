@@ -113,7 +113,7 @@ typedef struct cvvdp_clip {
   int32_t filter_len;           /* temporal filter length (video) */
   int32_t block_frames;         /* max frames per process_block call */
   int32_t heatmap;              /* CVVDP_HEATMAP_* */
-  int32_t debug_dump;           /* 1: keep per-pixel D of every band in the workspace (tests) */
+  int32_t debug_dump;           /* 1: keep per-pixel D of every band in the workspace (tests; cvvdp_dump_channels) */
   int32_t raw_halo;             /* 1: every block is handed its filter_len-1 predecessor frames as raw frames (hist_src >= 0),
                                    so no DKL tail is kept between blocks; 0: later blocks read the tail (hist_src < 0) */
   int32_t total_frames;         /* frames of the whole clip (all shards); 0 = unknown.  Sizes the band kernels' row segments:
@@ -433,6 +433,31 @@ int cvvdp_pixel_preview(cvvdp_handle* h, const void* dev_src, int32_t dtype, con
                         void* dev_dst, size_t dst_bytes, void* stream);
 /* sizeof(cvvdp_preview_args) as compiled. */
 int32_t cvvdp_preview_args_size(void);
+
+/* --dump-channels (pycvvdp/dump_channels.py: DumpChannels.dump_temp_ch :81-112, dump_lpyr :114-160, dump_diff :171-210, driven from
+ * cvvdp_metric.py:375-380, 676-677, 736-749): the reference's three debugging pictures of frames frame0 .. frame0+n_frames-1 of the block
+ * processed last, packed by the GPU from what a clip configured with debug_dump keeps in the workspace (the temporally filtered planes and
+ * their Gaussian pyramid, the per-pixel D of every band).  Batch item 0 only, like the reference.
+ *   CVVDP_DUMP_TEMPORAL  2H x 2W: test Y-sustained | test Y-transient over test RG | test YV through the reference's DKL -> RGB matrix with
+ *                        its white_dkl fill-ins and gray offset, divided by max_V; an image's transient quadrant is 0.2176 / max_V.  max_V is
+ *                        the largest linear RGB value of the Y-sustained quadrant of the CLIP'S FIRST FRAME: the call that holds that frame
+ *                        (first_frame + frame offset of the block + frame0 == 0) takes it and leaves it in the workspace, every later call
+ *                        of the clip reads it there (a call before that one is refused).  The reference takes the maximum over its first
+ *                        block, whose length depends on the free memory (one frame on the CPU): the first frame makes the picture
+ *                        independent of the block cut
+ *   CVVDP_DUMP_LPYR      ceil8((H0 + 1) * 2) x ceil8((W0 + W1 + 1) * 2), background 0: four quadrants (video: planes 0, 6, 2, 4; image: 0, 2,
+ *                        4), in each the contrast bands of weber_contrast_pyr.decompose (lpyr_dec.py:364-414, with get_band's gain) of the
+ *                        test side, laid out by the reference's walk: right after an even band, down after an odd one, one pixel apart
+ *   CVVDP_DUMP_DIFF      the same geometry, background 0.2716: D * per_ch_w * t_int / 10 as grey, quadrants = D channels 0, 3, 1, 2 (image:
+ *                        0, 1, 2); no baseband weight, unlike the heat map
+ * Common tail: x ** (1 / 2.2) * 255, clipped to [0, 255], truncated; a negative base gives code 0.  dev_dst receives uint8
+ * [n_frames][height][width][3] (interleaved RGB, sizes from cvvdp_dump_canvas_size; 4-byte aligned); dst_bytes is the size of the buffer
+ * behind it, and a call that would write outside it is refused.  Every byte of the n_frames canvases is written.  Valid only on a handle
+ * configured with debug_dump, after a block (or the image) has been processed; no scratch, no host synchronisation.
+ * ABI 14: added, nothing else changed. */
+enum { CVVDP_DUMP_TEMPORAL = 0, CVVDP_DUMP_LPYR = 1, CVVDP_DUMP_DIFF = 2 };
+int cvvdp_dump_canvas_size(const cvvdp_handle* h, int32_t which, int32_t* height, int32_t* width);
+int cvvdp_dump_channels(cvvdp_handle* h, int32_t which, int32_t frame0, int32_t n_frames, void* dev_dst, size_t dst_bytes, void* stream);
 
 /* Sources that deliver temporally pre-filtered channels (vid_source.is_temporally_filtered, cvvdp_metric.py:470-488):
  * frames are fp32 [B, 4, n, H, W] in colour space 'DKLd65_trans' (Y-sustained, RG, YV, Y-transient; element strides in
