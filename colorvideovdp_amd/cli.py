@@ -1,7 +1,7 @@
 """Command line of the MI355X build: `python -m colorvideovdp_amd` / `cvvdp` (console entry in pyproject.toml).
 
 Mirrors the reference's command line (pycvvdp/run_cvvdp.py:83-118 arguments, :120-371 run_on_args) for the path this build
-implements: the `cvvdp` metric, the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020`, the SSIM metric `ssim-metric`, the MS-SSIM metric
+implements: the `cvvdp` metric, its ML variant `cvvdp-ml-saliency` (below), the PSNR metrics `psnr-rgb`, `pu-psnr-y` and `pu-psnr-rgb2020`, the SSIM metric `ssim-metric`, the MS-SSIM metric
 `ms-ssim-metric` and the display-model previews `dm-preview`, `dm-preview-sbs`, `dm-preview-hdr` and `dm-preview-hdr-sbs` (fake metrics that write
 what the display model makes of both inputs into --output-dir and print -1; dm_preview_metric.py)
 (`-m cvvdp psnr-rgb ssim-metric ms-ssim-metric ...`, one output line and one CSV column per metric, in -m order) on image pairs (PNG / JPEG / anything Pillow reads, 8 or 16 bit; Radiance .hdr for HDR images, e.g. `-d standard_hdr_linear`), planar .yuv clips (the
@@ -16,7 +16,11 @@ JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpe
     temp_channels.mp4, lpyr.mp4 and diff.mp4 for a video through an ffmpeg pipe where an `ffmpeg` executable exists, otherwise
     `temp_channels_%05d.png` etc. with a warning; temp_channels.png, lpyr.png and diff.png for an image.  The pictures are packed on the
     GPU (dump_channels.py); with them the core scores on its unfused route, so the JOD printed equals the plain one to rounding;
-  * --device must be a cuda device; --temp-padding 'valid', the cvvdp-ml heads and the OpenEXR previews
+  * `-m cvvdp-ml-saliency` needs the two files of that model, which this package does not ship and never fetches: `-c DIR` with the
+    directory that holds the reference's `cvvdp_ml_saliency/cvvdp_parameters.json` and its `cvvdp.ckpt` (DIR itself, or DIR/cvvdp_ml_saliency).
+    Metrics named beside it do not take that parameter file for theirs.  It writes no --features file (a warning), no --distogram and no
+    heat map; `cvvdp-ml-transformer` is not available;
+  * --device must be a cuda device; --temp-padding 'valid', the cvvdp-ml-transformer head and the OpenEXR previews
     (dm-preview-exr, dm-preview-exr-sbs: dm-preview-hdr and dm-preview-hdr-sbs write the same values as Radiance .hdr) are not available; --full-screen-resize works for .yuv clips (as in the
     reference it is not implemented for images);
   * --temp-resample [X] scores .yuv clips whose file names carry different frame rates (a 30 fps encode against its 60 fps source) at
@@ -45,6 +49,8 @@ from . import psnr_metric  # noqa: F401  (registers psnr_rgb, pu_psnr_y, pu_psnr
 from . import ssim_metric  # noqa: F401  (registers ssim_metric)
 from . import ms_ssim_metric  # noqa: F401  (registers ms_ssim_metric)
 from . import dm_preview_metric  # noqa: F401  (registers dm_preview, dm_preview_sbs, dm_preview_hdr, dm_preview_hdr_sbs)
+from . import cvvdp_ml_metric  # noqa: F401  (registers cvvdp_ml_saliency)
+from .config import json2dict
 from .display_model import vvdp_display_geometry, vvdp_display_photometry
 from .video_source_file import IMAGE_EXT, VIDEO_EXT, load_image_as_array, video_source_file
 from .video_source_temp_resample import video_source_temp_resample_file
@@ -80,7 +86,7 @@ _OPTIONS = (
     (("--count-frames",), dict(action="store_true", default=False, help="accepted for compatibility (frame counts of .yuv / .npy inputs are exact)")),
     (("-f", "--full-screen-resize"), dict(choices=["bilinear", "bicubic", "nearest", "area"], default=None,
                                           help="resize test and reference to the display's resolution (.yuv clips; on the GPU, torch.nn.functional.interpolate semantics)")),
-    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, psnr-rgb, pu-psnr-y, pu-psnr-rgb2020, ssim-metric, ms-ssim-metric; "
+    (("-m", "--metric"), dict(nargs="+", default=["cvvdp"], help="metric(s): cvvdp, cvvdp-ml-saliency (with -c DIR: the directory of its cvvdp_parameters.json and cvvdp.ckpt), psnr-rgb, pu-psnr-y, pu-psnr-rgb2020, ssim-metric, ms-ssim-metric; "
                                    "dm-preview[-hdr][-sbs] write the display model's output as HDR video / Radiance .hdr files")),
     (("--temp-padding",), dict(choices=["replicate", "symmetric", "valid"], default="symmetric", help="padding before the first frame ('valid': " + _NA + ")")),
     (("--pix-per-deg",), dict(type=float, default=None, help="override the display geometry")),
@@ -140,6 +146,25 @@ def metric_arguments(metric_class, **available):
     config_paths of pu_psnr_y and makes `-m pu-psnr-rgb2020` fail with a TypeError."""
     names = set(inspect.getfullargspec(metric_class.__init__)[0])
     return {k: v for k, v in available.items() if k in names}
+
+
+def metric_config_paths(metric_name, config_paths):
+    """The -c paths as metric `metric_name` gets them.  A directory made for a cvvdp-ml metric holds a cvvdp_parameters.json of THAT model
+    (its `internal_model_name`); every other metric would take it for its own parameter file.  For them such a directory is replaced
+    by the other .json files in it, so `-m cvvdp cvvdp-ml-saliency -c DIR` scores each metric with its own parameters."""
+    out = []
+    for cp in config_paths:
+        pfile = os.path.join(cp, "cvvdp_parameters.json")
+        if os.path.isdir(cp) and os.path.isfile(pfile):
+            try:
+                model = json2dict(pfile).get("internal_model_name")
+            except (ValueError, AttributeError):
+                model = None
+            if isinstance(model, str) and model.startswith("cvvdp_ml") and model != metric_name:
+                out += sorted(os.path.join(cp, f) for f in os.listdir(cp) if f.endswith(".json") and f != "cvvdp_parameters.json")
+                continue
+        out.append(cp)
+    return out
 
 
 def run_on_args(args):
@@ -211,7 +236,7 @@ def run_on_args(args):
             raise RuntimeError(f"Unknown metric {mm}")
         fv = vq_metric_dict[mm](**metric_arguments(vq_metric_dict[mm], display_photometry=display_photometry, display_geometry=display_geometry,
                                                    device=device, heatmap=args.heatmap, temp_padding=args.temp_padding,
-                                                   config_paths=args.config_paths, gpu_mem=args.gpu_mem, quiet=args.quiet, verbose=args.verbose,
+                                                   config_paths=metric_config_paths(mm, args.config_paths), gpu_mem=args.gpu_mem, quiet=args.quiet, verbose=args.verbose,
                                                    dump_channels=dump_channels))
         fv.train(False)
         metrics.append(fv)
@@ -256,7 +281,9 @@ def run_on_args(args):
                 print(f"{q:0.4f}" if args.quiet else f"{mm.short_name()}={q:0.4f} [{mm.quality_unit()}]")
                 if res_fh is not None:
                     res_fh.write(f", {q}")
-                if args.features and stats is not None:
+                if args.features and stats is not None and "Q_per_ch" not in stats:
+                    logging.warning(f"Skipping features as it is not supported by {mm.short_name()}")      # run_cvvdp.py:342-343
+                elif args.features and stats is not None:
                     dest = os.path.join(out_dir, base + "_fmap.json")
                     logging.info("Writing feature map '" + dest + "' ...")
                     mm.write_features_to_json(stats, dest)

@@ -935,6 +935,28 @@ int cvvdp::rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int
   return CVVDP_OK;
 }
 int cvvdp::rgbe_check_launch(cvvdp_handle* h) { return check_launch(h, "unpack_rgbe"); }
+// cvvdp_ml_saliency_head (ml_head.hip) up to the launch
+int cvvdp::ml_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C, const float* weights, float scale,
+                           uint32_t mask, float* q, void* scratch, size_t scratch_bytes, MlHeadArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!feat || !weights || !q || !scratch) return fail(h, CVVDP_E_ARG, "ml_saliency_head: null argument");
+  if (B < 1 || F < 1 || Hc < 1 || Wc < 1) return fail(h, CVVDP_E_ARG, "ml_saliency_head: bad geometry B=%d F=%d cells %dx%d", B, F, Wc, Hc);
+  if (C != 3 && C != 4) return fail(h, CVVDP_E_ARG, "ml_saliency_head: C = %d, a cell has 3 (image) or 4 (video) channels", C);
+  if (mask > 63u) return fail(h, CVVDP_E_ARG, "ml_saliency_head: disabled_mask %u names a statistic beyond the six", mask);
+  if (!std::isfinite(scale)) return fail(h, CVVDP_E_ARG, "ml_saliency_head: scale is not finite");
+  const int64_t FH = (int64_t)F * Hc, per = FH > 0x7fffffff ? FH : FH * Wc;
+  if (per > 0x7fffffff / (int64_t)B - kMlThreads) return fail(h, CVVDP_E_ARG, "ml_saliency_head: %lld cells per item x %d items are too many", (long long)per, B);
+  if (reinterpret_cast<uintptr_t>(feat) % (C == 4 ? 16 : 8)) return fail(h, CVVDP_E_ARG, "ml_saliency_head: features not %d-byte aligned", C == 4 ? 16 : 8);
+  if (reinterpret_cast<uintptr_t>(weights) % 16 || reinterpret_cast<uintptr_t>(q) % 4 || reinterpret_cast<uintptr_t>(scratch) % 4)
+    return fail(h, CVVDP_E_ARG, "ml_saliency_head: weights must be 16-byte aligned, the sums and the scratch 4-byte aligned");
+  const int32_t K = ml_head_parts(per);
+  if (scratch_bytes < (size_t)B * K * sizeof(float)) return fail(h, CVVDP_E_ARG, "ml_saliency_head: scratch of %zu bytes, %zu needed", scratch_bytes, (size_t)B * K * sizeof(float));
+  a = MlHeadArgs{};
+  a.feat = feat; a.weights = weights; a.partial = static_cast<float*>(scratch); a.q = q;
+  a.n_cells = (int32_t)(per * B); a.per_item = (int32_t)per; a.B = B; a.K = K; a.C = C; a.mask = mask; a.scale = scale;
+  return CVVDP_OK;
+}
+int cvvdp::ml_head_check_launch(cvvdp_handle* h) { return check_launch(h, "ml_saliency_head"); }
 // cvvdp_pixel_preview (preview.hip) up to the launch: the source checks of cvvdp_pixel_sse on one side, then the target, the format and
 // the canvas.  Nothing is launched unless the last pixel of the last frame lies inside dst_bytes.
 int cvvdp::preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref,

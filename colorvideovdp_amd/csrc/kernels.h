@@ -520,4 +520,32 @@ void launch_dump_temporal(const DumpTemporalArgs& a, hipStream_t s);
 void launch_dump_lpyr(const DumpLpyrArgs& a, bool baseband, hipStream_t s);
 void launch_dump_diff(const DumpDiffArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- cvvdp-ml-saliency head (ml_head.hip)
+// Two MLPs per feature cell (cvvdp_ml_metric.py:496-547).  The packed weights (CVVDP_ML_WEIGHTS floats, include/cvvdp_hip.h): per
+// Linear layer W[out][in] row-major, then bias[out]; att_net at float 0, feature_net at kMlFeatOff.  Every layer and every row of W
+// starts at a multiple of 4 floats, so the LDS image is read with 16-byte loads.
+constexpr int kMlThreads = 256;
+constexpr int kMlAttIn = 16, kMlAttHid = 48, kMlFeatIn = 8, kMlFeatHid = 24;
+constexpr int kMlAttFloats = (kMlAttIn + 1) * kMlAttHid + 3 * (kMlAttHid + 1) * kMlAttHid + kMlAttHid + 1;        // 7921
+constexpr int kMlFeatFloats = (kMlFeatIn + 1) * kMlFeatHid + 2 * (kMlFeatHid + 1) * kMlFeatHid + kMlFeatHid + 1;  // 1441
+constexpr int kMlFeatOff = (kMlAttFloats + 3) / 4 * 4;                                                             // 7924
+constexpr int kMlWeights = (kMlFeatOff + kMlFeatFloats + 3) / 4 * 4;                                               // 9368
+static_assert(kMlWeights == CVVDP_ML_WEIGHTS && kMlFeatOff == CVVDP_ML_FEATURE_NET_OFFSET, "packing of the head's weights");
+struct MlHeadArgs {
+  const float* feat;        // [n_cells][C][6]
+  const float* weights;     // kMlWeights floats, 16-byte aligned
+  float* partial;           // [B][K]: partial[b][k] = the sum over the cells of item b in the k-th block that holds some
+  float* q;                 // [B]: q[b] -= mean over the cells of item b
+  int32_t n_cells, per_item, B, K, C;
+  uint32_t mask;            // bit s: statistic s of every channel counts as 0
+  float scale;
+};
+// partial sums per batch item: an item of per_item cells starts anywhere in a block, so it touches at most this many blocks
+inline int32_t ml_head_parts(int64_t per_item) { return (int32_t)((per_item - 1) / kMlThreads + 2); }
+// core.cpp: argument checks and kernel arguments of cvvdp_ml_saliency_head; the error of a launch
+int ml_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C, const float* weights, float scale,
+                    uint32_t mask, float* q, void* scratch, size_t scratch_bytes, MlHeadArgs& a);
+int ml_head_check_launch(cvvdp_handle* h);
+void launch_ml_head(const MlHeadArgs& a, hipStream_t s);
+
 }  // namespace cvvdp

@@ -394,6 +394,35 @@ const char* cvvdp_rgbe_strerror(int code);
 int cvvdp_unpack_rgbe(cvvdp_handle* h, const void* dev_rgbe, int32_t n_frames, int32_t H, int32_t W, float* dev_out, int64_t stride_c,
                       int64_t stride_f, void* stream);
 
+/* Head of the cvvdp-ml-saliency metric (cvvdp_ml_saliency.do_pooling_and_jods, pycvvdp/cvvdp_ml_metric.py:496-547) for ONE band of the
+ * features cvvdp_get_features delivers.  Per cell of dev_features (fp32 [B][F][Hc][Wc][C][6], contiguous: mean_T, var_T, mean_R, var_R,
+ * mean_D, var_D per channel; C = 4 for a video, C = 3 for an image, whose missing transient channel counts as zeros):
+ *   the variances become standard deviations, sqrt(|v|) (:516); then statistic s of every channel is 0 where bit s of disabled_mask
+ *   is set (disabled_features, :520-521);
+ *   Att = relu(att_net(16 inputs: statistics 0..3, channel-major)), att_net = Linear 16 -> 48, 48 -> 48 three times, 48 -> 1, a
+ *   ReLU after all but the last (:523, :526-527);
+ *   D = relu(feature_net(8 inputs: statistics 4..5, channel-major)) * Att * scale, feature_net = Linear 8 -> 24, 24 -> 24 twice,
+ *   24 -> 1 (:524, :528-536); scale = (1 / bands) * (baseband_weight on the last band) * (image_int for an image), the caller's product;
+ * and per batch item dev_q[b] = dev_q[b] - mean of D over the item's F * Hc * Wc cells (:538, :546-547), in fp32 like the reference's
+ * Q_JOD: the caller fills dev_q (float [B]) with 10 and calls once per band, in band order.
+ *   dev_weights   CVVDP_ML_WEIGHTS floats, 16-byte aligned.  Per Linear layer its weight [out][in] row-major (the layout of
+ *                 torch.nn.Linear.weight) followed by its bias [out]; the five layers of att_net from float 0 (7921 floats), three
+ *                 floats of padding, the four layers of feature_net from float CVVDP_ML_FEATURE_NET_OFFSET (1441 floats), three
+ *                 floats of padding
+ *   dev_scratch   the scratch size function's bytes for (B, F, Hc, Wc), 4-byte aligned: one float per (batch item, block of cells)
+ * dev_features is 16-byte aligned for C = 4 and 8-byte aligned for C = 3, and is only read.  fp32 FMAs, per output one accumulator
+ * that starts at the bias and takes the inputs in index order.  A cell's D is summed within a wave, the waves in order, per item the
+ * block sums in block order in double; no atomics, so every call gives the same bits, and the launch geometry depends on the shape
+ * alone.  Invalid arguments (C not 3 or 4, a null pointer, a size below 1, more than 2^31 cells, a short scratch) give CVVDP_E_ARG
+ * before any launch.  Needs no configured clip and touches no handle state (the handle carries the error text).  ABI 14: added,
+ * nothing else changed. */
+#define CVVDP_ML_WEIGHTS 9368
+#define CVVDP_ML_FEATURE_NET_OFFSET 7924
+size_t cvvdp_ml_saliency_head_scratch_bytes(int32_t B, int32_t F, int32_t Hc, int32_t Wc);
+int cvvdp_ml_saliency_head(cvvdp_handle* h, const float* dev_features, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C,
+                           const float* dev_weights, float scale, uint32_t disabled_mask, float* dev_q, void* dev_scratch,
+                           size_t scratch_bytes, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
