@@ -19,8 +19,8 @@ JSON, --distogram PNG, --heatmap).  Differences, because this image has no ffmpe
   * `-m cvvdp-ml-saliency` needs the two files of that model, which this package does not ship and never fetches: `-c DIR` with the
     directory that holds the reference's `cvvdp_ml_saliency/cvvdp_parameters.json` and its `cvvdp.ckpt` (DIR itself, or DIR/cvvdp_ml_saliency).
     Metrics named beside it do not take that parameter file for theirs.  It writes no --features file (a warning), no --distogram and no
-    heat map; `cvvdp-ml-transformer` is not available;
-  * --device must be a cuda device; --temp-padding 'valid', the cvvdp-ml-transformer head and the OpenEXR previews
+    heat map; `cvvdp-ml-transformer` (the class `cvvdp_ml_transformer`) is available from Python only; not yet on the command line;
+  * --device must be a cuda device; --temp-padding 'valid' and the OpenEXR previews
     (dm-preview-exr, dm-preview-exr-sbs: dm-preview-hdr and dm-preview-hdr-sbs write the same values as Radiance .hdr) are not available; --full-screen-resize works for .yuv clips (as in the
     reference it is not implemented for images);
   * --temp-resample [X] scores .yuv clips whose file names carry different frame rates (a 30 fps encode against its 60 fps source) at

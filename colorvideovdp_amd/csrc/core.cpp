@@ -957,6 +957,33 @@ int cvvdp::ml_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_
   return CVVDP_OK;
 }
 int cvvdp::ml_head_check_launch(cvvdp_handle* h) { return check_launch(h, "ml_saliency_head"); }
+// cvvdp_ml_transformer_head (ml_transformer.hip) up to the launch
+int cvvdp::mt_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C, const float* weights, float scale,
+                           uint32_t mask, float* q, float* y, void* scratch, size_t scratch_bytes, MtHeadArgs& a) {
+  if (!h) return CVVDP_E_STATE;
+  if (!feat || !weights || !q || !scratch) return fail(h, CVVDP_E_ARG, "ml_transformer_head: null argument");
+  if (B < 1 || F < 1 || Hc < 1 || Wc < 1) return fail(h, CVVDP_E_ARG, "ml_transformer_head: bad geometry B=%d F=%d cells %dx%d", B, F, Wc, Hc);
+  if (C != 3 && C != 4) return fail(h, CVVDP_E_ARG, "ml_transformer_head: C = %d, a cell has 3 (image) or 4 (video) channels", C);
+  if (mask > 63u) return fail(h, CVVDP_E_ARG, "ml_transformer_head: disabled_mask %u names a statistic beyond the six", mask);
+  if (!std::isfinite(scale)) return fail(h, CVVDP_E_ARG, "ml_transformer_head: scale is not finite");
+  int64_t N, S;
+  if (!mt_head_geometry(B, F, Hc, Wc, N, S))
+    return fail(h, CVVDP_E_ARG, "ml_transformer_head: %d x %d sequences of %lld tokens are too many", B, F, (long long)Hc * Wc + 1);
+  if (reinterpret_cast<uintptr_t>(weights) % 16 || reinterpret_cast<uintptr_t>(scratch) % 16)
+    return fail(h, CVVDP_E_ARG, "ml_transformer_head: weights and scratch must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(feat) % 4 || reinterpret_cast<uintptr_t>(q) % 4 || reinterpret_cast<uintptr_t>(y) % 4)
+    return fail(h, CVVDP_E_ARG, "ml_transformer_head: features, q and y must be 4-byte aligned");
+  const size_t need = mt_head_scratch(B, F, N, S);
+  if (scratch_bytes < need) return fail(h, CVVDP_E_ARG, "ml_transformer_head: scratch of %zu bytes, %zu needed", scratch_bytes, need);
+  a = MtHeadArgs{};
+  float* s = static_cast<float*>(scratch);
+  const size_t ny = ((size_t)B * F + 3) / 4 * 4, M = (size_t)S * N;
+  a.feat = feat; a.w = weights; a.q = q; a.y = y ? y : s;
+  a.x = s + ny; a.att = a.x + M * kMtDim; a.buf = a.att + M * kMtDim; a.cls = a.buf + M * kMtFf; a.st = a.cls + (size_t)S * kMtClsRow;
+  a.B = B; a.F = F; a.C = C; a.N = (int32_t)N; a.S = (int32_t)S; a.mask = mask; a.scale = scale;
+  return CVVDP_OK;
+}
+int cvvdp::mt_head_check_launch(cvvdp_handle* h) { return check_launch(h, "ml_transformer_head"); }
 // cvvdp_pixel_preview (preview.hip) up to the launch: the source checks of cvvdp_pixel_sse on one side, then the target, the format and
 // the canvas.  Nothing is launched unless the last pixel of the last frame lies inside dst_bytes.
 int cvvdp::preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref,

@@ -548,4 +548,53 @@ int ml_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, in
 int ml_head_check_launch(cvvdp_handle* h);
 void launch_ml_head(const MlHeadArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- cvvdp-ml-transformer head (ml_transformer.hip)
+// A 4-layer, 256-wide, 8-head pre-norm encoder over the cells of a frame (cvvdp_ml_metric.py:553-678).  The packed weights
+// (CVVDP_MT_WEIGHTS floats, include/cvvdp_hip.h): every matrix transposed to [in][out], so that a row of it is contiguous in the
+// output index; every part starts at a multiple of 4 floats.
+constexpr int kMtDim = 256, kMtFf = 1024, kMtLayers = 4;
+constexpr int kMtOffCls = 0, kMtOffEmbW = kMtDim, kMtOffEmbB = kMtOffEmbW + 24 * kMtDim, kMtOffLayer0 = kMtOffEmbB + kMtDim;      // 0, 256, 6400, 6656
+// within a layer: norm1 (weight, bias), in_proj, out_proj, norm2 (weight, bias), linear1, linear2; a matrix, then its bias
+constexpr int kMtLLn1 = 0, kMtLWqkv = 2 * kMtDim, kMtLBqkv = kMtLWqkv + 3 * kMtDim * kMtDim, kMtLWo = kMtLBqkv + 3 * kMtDim,
+              kMtLBo = kMtLWo + kMtDim * kMtDim, kMtLLn2 = kMtLBo + kMtDim, kMtLW1 = kMtLLn2 + 2 * kMtDim, kMtLB1 = kMtLW1 + kMtDim * kMtFf,
+              kMtLW2 = kMtLB1 + kMtFf, kMtLB2 = kMtLW2 + kMtFf * kMtDim, kMtLayerFloats = kMtLB2 + kMtDim;                        // 789760
+constexpr int kMtOffReg = kMtOffLayer0 + kMtLayers * kMtLayerFloats;                // reg_head: norm weight, norm bias, weight [256], bias [1]
+constexpr int kMtWeights = (kMtOffReg + 3 * kMtDim + 1 + 3) / 4 * 4;                // 3166468
+static_assert(kMtWeights == CVVDP_MT_WEIGHTS && kMtLayerFloats == 789760 && kMtOffReg + 3 * kMtDim + 1 == 3166465, "packing of the transformer's weights");
+constexpr int64_t kMtCapTokens = CVVDP_MT_CHUNK_TOKENS;      // tokens of one chunk of sequences (a longer sequence is a chunk of its own)
+constexpr int64_t kMtRowFloats = 2 * kMtDim + kMtFf + 2;     // scratch per token: x, att, buf and the LayerNorm statistics
+constexpr int64_t kMtClsRow = 3 * kMtDim + kMtFf;            // the last layer's cls row of a sequence: x, q, att, hidden
+constexpr int64_t kMtClsFloats = kMtClsRow + 2;              // scratch per sequence: that row and its LayerNorm statistics
+struct MtHeadArgs {
+  const float* feat;        // [B * F][N - 1][C][6]
+  const float* w;           // kMtWeights floats, 16-byte aligned
+  float* q;                 // [B]
+  float* y;                 // [B * F]: the caller's, or the head of the scratch
+  float *x, *buf, *att;     // [S * N][256], [S * N][1024], [S * N][256]
+  float* st;                // [S * N + S][2]: mean and 1 / sqrt(var + eps) of the rows, then of the cls rows
+  float* cls;               // [S][1792]: the last layer's cls rows, x | q | att | hidden
+  int32_t B, F, C, N, S;    // N tokens per sequence, S sequences per chunk
+  uint32_t mask;
+  float scale;
+};
+// N and S of a band; false where a size is below 1 or the band has more than 2^31 - 1 tokens
+inline bool mt_head_geometry(int32_t B, int32_t F, int32_t Hc, int32_t Wc, int64_t& N, int64_t& S) {
+  if (B < 1 || F < 1 || Hc < 1 || Wc < 1) return false;
+  N = (int64_t)Hc * Wc + 1;
+  const int64_t n_seq = (int64_t)B * F;
+  if (n_seq > 0x7fffffff || N > 0x7fffffff / n_seq) return false;
+  S = kMtCapTokens / N;
+  if (S < 1) S = 1;
+  if (S > n_seq) S = n_seq;
+  return true;
+}
+inline size_t mt_head_scratch(int32_t B, int32_t F, int64_t N, int64_t S) {
+  const size_t ny = ((size_t)B * F + 3) / 4 * 4;
+  return (ny + (size_t)S * N * kMtRowFloats + (size_t)S * kMtClsFloats) * sizeof(float);
+}
+int mt_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C, const float* weights, float scale,
+                    uint32_t mask, float* q, float* y, void* scratch, size_t scratch_bytes, MtHeadArgs& a);
+int mt_head_check_launch(cvvdp_handle* h);
+void launch_mt_head(const MtHeadArgs& a, hipStream_t s);
+
 }  // namespace cvvdp

@@ -1,16 +1,23 @@
-"""ColorVideoVDP-ML-Saliency (pycvvdp/cvvdp_ml_metric.py:463-550 `class cvvdp_ml_saliency`) for MI355X: the base model's pooled
-per-band features (`cvvdp.extract_features`) scored by two small MLPs, a saliency ("attention") net on the statistics of test and
-reference and a difference net on the statistics of D, at every feature cell.
+"""The ML heads of ColorVideoVDP (pycvvdp/cvvdp_ml_metric.py) for MI355X, on the base model's pooled per-band features
+(`cvvdp.extract_features`):
 
-Same constructor arguments, methods, names and errors as the reference class.  The features come from the band kernels' feature
-route, unchanged; the head is one HIP pass per band (cvvdp_ml_saliency_head, include/cvvdp_hip.h; csrc/ml_head.hip).
+  cvvdp_ml_saliency      (:463-550) two small MLPs at every feature cell, a saliency ("attention") net on the statistics of test and
+                         reference and a difference net on the statistics of D.  One HIP pass per band (cvvdp_ml_saliency_head,
+                         include/cvvdp_hip.h; csrc/ml_head.hip).
+  cvvdp_ml_transformer   (:553-678) a 4-layer, 256-wide, 8-head pre-norm transformer encoder over all cells of a frame, read out at a
+                         cls token.  HIP kernels on the fp32 matrix instructions (cvvdp_ml_transformer_head; csrc/ml_transformer.hip).
+                         From Python only; not yet on the command line.
+
+Same constructor arguments, methods, names and errors as the reference classes.  The features come from the band kernels' feature
+route, unchanged.
 
 Where the two files of the model come from: the reference package ships `vvdp_data/cvvdp_ml_saliency/cvvdp_parameters.json` and fetches
-the trained networks, `cvvdp_ml_saliency/cvvdp.ckpt`, when its class is first constructed.  This package ships neither and fetches
-nothing: the directory that holds both is passed as `config_paths=[dir]` (`-c dir` on the command line).  A `cvvdp_ml_saliency`
-sub-directory of a configuration directory is looked into first, so the parent of the reference's layout works as well.
+the trained networks, `cvvdp_ml_saliency/cvvdp.ckpt`, when its class is first constructed (and likewise under `cvvdp_ml_transformer`).
+This package ships neither and fetches nothing: the directory that holds both is passed as `config_paths=[dir]` (`-c dir` on the
+command line).  A sub-directory of a configuration directory with the model's name is looked into first, so the parent of the
+reference's layout works as well.
 
-Not available: `cvvdp_ml_transformer` (a 4-layer transformer encoder over all cells of a frame), heat maps, distograms, frame sharding.
+Not available: heat maps, distograms, frame sharding, `RegressionTransformer.get_heatmap`, training.
 """
 import ctypes
 import logging
@@ -88,7 +95,12 @@ def pack_weights(nets):
     return out
 
 
-class cvvdp_ml_saliency(cvvdp):
+class _cvvdp_ml(cvvdp):
+    """What the ML metrics share: the constructor's refusals, the model directory, the display-model swap of predict_video_source.  A
+    metric names its model (`_MODEL`, `_TITLE`), makes and validates its networks (`_random_nets`, `_nets_from_state_dict`, `_set_nets`) and
+    scores the features (`do_pooling_and_jods`)."""
+    _MODEL = _TITLE = _WHERE = None
+
     def __init__(self, display_name="standard_4k", display_photometry=None, display_geometry=None, config_paths=[], heatmap=None, quiet=False,
                  device=None, temp_padding="replicate", use_checkpoints=False, dump_channels=None, gpu_mem=None, block_frames=None,
                  random_init=False, disabled_features=None):
@@ -115,55 +127,37 @@ class cvvdp_ml_saliency(cvvdp):
         and by heat maps, neither of which this metric runs: the features carry no baseband weight) and gets the scalar four times."""
         if not isinstance(config_paths, list):
             raise RuntimeError("config_paths must be a list")
-        own = [os.path.join(cp, "cvvdp_ml_saliency") for cp in config_paths if os.path.isdir(os.path.join(cp, "cvvdp_ml_saliency"))]
+        model, title, where = self._MODEL, self._TITLE, self._WHERE
+        own = [os.path.join(cp, model) for cp in config_paths if os.path.isdir(os.path.join(cp, model))]
         try:
             pfile = config_files.find("cvvdp_parameters.json", own + config_paths)
         except RuntimeError as e:
-            raise vq_exception(f"{e}. {_WHERE}") from None
+            raise vq_exception(f"{e}. {where}") from None
         if pfile.startswith("builtin:"):
-            raise vq_exception("The parameter file of cvvdp-ml-saliency (cvvdp_parameters.json with internal_model_name 'cvvdp_ml_saliency') was not "
-                               f"found in the configuration paths. {_WHERE}")
+            raise vq_exception(f"The parameter file of {title} (cvvdp_parameters.json with internal_model_name '{model}') was not "
+                               f"found in the configuration paths. {where}")
         p = dict(json2dict(pfile))
         bw = p.get("baseband_weight")
-        if p.get("internal_model_name") != "cvvdp_ml_saliency" or isinstance(bw, (list, tuple)):
-            raise vq_exception(f"'{pfile}' is not the parameter file of cvvdp-ml-saliency (internal_model_name "
-                               f"'{p.get('internal_model_name')}': the base model's file?). {_WHERE}")
+        if p.get("internal_model_name") != model or isinstance(bw, (list, tuple)):
+            raise vq_exception(f"'{pfile}' is not the parameter file of {title} (internal_model_name "
+                               f"'{p.get('internal_model_name')}': the base model's file?). {where}")
         if isinstance(bw, (str, bool)) or bw is None or not np.isfinite(float(bw)):
-            raise RuntimeError("parameter 'baseband_weight' of cvvdp-ml-saliency must be a finite number")
+            raise RuntimeError(f"parameter 'baseband_weight' of {title} must be a finite number")
         if self.random_init:
-            nets = random_nets()
+            nets = self._random_nets()
         else:
             try:
                 ckpt = config_files.find("cvvdp.ckpt", own + config_paths)
             except RuntimeError:
-                raise vq_exception(f"The checkpoint of cvvdp-ml-saliency (cvvdp.ckpt) was not found in the configuration paths. {_WHERE}") from None
+                raise vq_exception(f"The checkpoint of {title} (cvvdp.ckpt) was not found in the configuration paths. {where}") from None
             logging.info(f"Loading cvvdp checkpoint file from {ckpt}")
-            nets = nets_from_state_dict(torch.load(ckpt, map_location="cpu")["state_dict"])
+            nets = self._nets_from_state_dict(torch.load(ckpt, map_location="cpu")["state_dict"])
         self.parameters_file = pfile
         self._config_paths = list(config_paths)
         p["baseband_weight"] = [float(bw)] * 4
         self._set_parameters(p)
         self._ml_baseband_weight = f32(bw)
         self._set_nets(nets)
-
-    def _set_nets(self, nets):
-        self._nets = nets
-        self._packed = pack_weights(nets)
-        self._weights_dev = None
-
-    def load_state_dict_nets(self, state_dict):
-        """Replace both networks from a state dict with `att_net.<i>.weight` / `.bias` and `feature_net.<i>.weight` / `.bias` entries
-        (what a checkpoint's `state_dict` holds); validated like a checkpoint, and nothing changes if it does not validate."""
-        self._set_nets(nets_from_state_dict(state_dict))
-
-    def state_dict_nets(self):
-        """The networks as a state dict with torchvision's layer indices (0, 3, 6, ...)."""
-        return {f"{net}.{3 * k}.{kind}": t.clone() for net, layers in self._nets.items() for k, wb in enumerate(layers)
-                for kind, t in zip(("weight", "bias"), wb)}
-
-    def packed_weights(self):
-        """float32 [ML_WEIGHTS]: the buffer the kernel reads (pack_weights)."""
-        return self._packed.copy()
 
     def set_frame_sharding(self, group="world"):
         if group is not None:
@@ -202,16 +196,65 @@ class cvvdp_ml_saliency(cvvdp):
                  "N_frames": N_frames}
         return (Q_jod.squeeze(), stats)
 
-    def do_pooling_and_jods(self, features):
-        """cvvdp_ml_saliency.do_pooling_and_jods (cvvdp_ml_metric.py:496-541): features[band] is [B, F, H', W', C, 6] (any list of such
-        tensors; C = 3 marks an image) -> Q_JOD[B] on the device.  One cvvdp_ml_saliency_head call per band; unlike the reference's,
-        this one leaves the caller's tensors as they are."""
+    def _check_features(self, features):
+        """B, C and an iterator over the bands (the features as a contiguous fp32 device tensor, the head's scale: 1 / bands, times the model's
+        baseband_weight on the last band, times image_int for an image) of a list of [B, F, H', W', C, 6] tensors."""
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
         no_bands = len(features)
         if no_bands < 1:
             raise ValueError("do_pooling_and_jods: no bands")
         B, C = int(features[0].shape[0]), int(features[0].shape[4])
+
+        def bands():                                    # one band on the device at a time
+            for bb, f in enumerate(features):
+                f = torch.as_tensor(f).to(self.device, torch.float32).contiguous()
+                if f.dim() != 6 or f.shape[5] != 6 or f.shape[0] != B or f.shape[4] != C:
+                    raise ValueError(f"features[{bb}] has shape {tuple(f.shape)}, expected [{B}, F, H', W', {C}, 6]")
+                scale = 1.0 / no_bands
+                if bb == no_bands - 1:
+                    scale *= float(self._ml_baseband_weight)
+                if C == 3:
+                    scale *= float(f32(self.parameters["image_int"]))
+                yield f, scale
+        return B, C, bands()
+
+    def short_name(self):
+        return self.__class__.__name__.replace("_", "-")
+
+    def export_distogram(self, stats, fname, jod_max=None, base_size=6):
+        raise vq_exception("Currently cvvdp-ml metrics do not export distograms")
+
+
+class cvvdp_ml_saliency(_cvvdp_ml):
+    _MODEL, _TITLE, _WHERE = "cvvdp_ml_saliency", "cvvdp-ml-saliency", _WHERE
+    _random_nets = staticmethod(random_nets)
+    _nets_from_state_dict = staticmethod(nets_from_state_dict)
+
+    def _set_nets(self, nets):
+        self._nets = nets
+        self._packed = pack_weights(nets)
+        self._weights_dev = None
+
+    def load_state_dict_nets(self, state_dict):
+        """Replace both networks from a state dict with `att_net.<i>.weight` / `.bias` and `feature_net.<i>.weight` / `.bias` entries
+        (what a checkpoint's `state_dict` holds); validated like a checkpoint, and nothing changes if it does not validate."""
+        self._set_nets(nets_from_state_dict(state_dict))
+
+    def state_dict_nets(self):
+        """The networks as a state dict with torchvision's layer indices (0, 3, 6, ...)."""
+        return {f"{net}.{3 * k}.{kind}": t.clone() for net, layers in self._nets.items() for k, wb in enumerate(layers)
+                for kind, t in zip(("weight", "bias"), wb)}
+
+    def packed_weights(self):
+        """float32 [ML_WEIGHTS]: the buffer the kernel reads (pack_weights)."""
+        return self._packed.copy()
+
+    def do_pooling_and_jods(self, features):
+        """cvvdp_ml_saliency.do_pooling_and_jods (cvvdp_ml_metric.py:496-541): features[band] is [B, F, H', W', C, 6] (any list of such
+        tensors; C = 3 marks an image) -> Q_JOD[B] on the device.  One cvvdp_ml_saliency_head call per band; unlike the reference's,
+        this one leaves the caller's tensors as they are."""
+        B, C, bands = self._check_features(features)
         if self._weights_dev is None:
             self._weights_dev = torch.from_numpy(self._packed).to(self.device)
         mask = sum(1 << s for s in set(self.disabled_features or ()))
@@ -219,17 +262,9 @@ class cvvdp_ml_saliency(cvvdp):
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):
             Q = torch.full((B,), 10.0, dtype=torch.float32, device=self.device)
-            for bb, f in enumerate(features):
-                f = torch.as_tensor(f).to(self.device, torch.float32).contiguous()
-                if f.dim() != 6 or f.shape[5] != 6 or f.shape[0] != B or f.shape[4] != C:
-                    raise ValueError(f"features[{bb}] has shape {tuple(f.shape)}, expected [{B}, F, H', W', {C}, 6]")
+            for f, scale in bands:
                 if f.data_ptr() % (16 if C == 4 else 8):           # (a view into a larger buffer: the kernel reads 16 / 8 bytes at a time)
                     f = f.clone()
-                scale = 1.0 / no_bands
-                if bb == no_bands - 1:
-                    scale *= float(self._ml_baseband_weight)
-                if C == 3:
-                    scale *= float(f32(self.parameters["image_int"]))
                 _, F, Hc, Wc = (int(n) for n in f.shape[:4])
                 nbytes = lib.cvvdp_ml_saliency_head_scratch_bytes(B, F, Hc, Wc)
                 scratch = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
@@ -241,11 +276,153 @@ class cvvdp_ml_saliency(cvvdp):
     def full_name(self):
         return "ColorVideoVDP-ML-Saliency"
 
-    def short_name(self):
-        return self.__class__.__name__.replace("_", "-")
-
-    def export_distogram(self, stats, fname, jod_max=None, base_size=6):
-        raise vq_exception("Currently cvvdp-ml metrics do not export distograms")
-
 
 register_metric(cvvdp_ml_saliency)
+
+
+# ---------------------------------------------------------------------------------------------------------------- cvvdp-ml-transformer
+MT_DIM, MT_HEADS, MT_FF, MT_LAYERS, MT_INPUTS = 256, 8, 1024, 4, 24
+
+
+def transformer_entries():
+    """[(key, shape)] of the 55 entries of RegressionTransformer(in_channels=24, dim=256) (cvvdp_ml_metric.py:553-587), in the order
+    of its state dict."""
+    e = [("cls_token", (1, 1, MT_DIM)), ("patch_embed.1.weight", (MT_DIM, MT_INPUTS)), ("patch_embed.1.bias", (MT_DIM,))]
+    for l in range(MT_LAYERS):
+        p = f"transformer.layers.{l}."
+        e += [(p + "self_attn.in_proj_weight", (3 * MT_DIM, MT_DIM)), (p + "self_attn.in_proj_bias", (3 * MT_DIM,)),
+              (p + "self_attn.out_proj.weight", (MT_DIM, MT_DIM)), (p + "self_attn.out_proj.bias", (MT_DIM,)),
+              (p + "linear1.weight", (MT_FF, MT_DIM)), (p + "linear1.bias", (MT_FF,)),
+              (p + "linear2.weight", (MT_DIM, MT_FF)), (p + "linear2.bias", (MT_DIM,)),
+              (p + "norm1.weight", (MT_DIM,)), (p + "norm1.bias", (MT_DIM,)), (p + "norm2.weight", (MT_DIM,)), (p + "norm2.bias", (MT_DIM,))]
+    return e + [("reg_head.0.weight", (MT_DIM,)), ("reg_head.0.bias", (MT_DIM,)), ("reg_head.1.weight", (1, MT_DIM)), ("reg_head.1.bias", (1,))]
+
+
+def transformer_from_state_dict(state_dict):
+    """{key without the `transformer_net.` prefix: float32 CPU tensor} of the 55 entries, from a state dict that holds them under
+    `transformer_net.` (what a checkpoint's `state_dict` holds).  A missing entry, a wrong shape or an entry under `transformer_net.`
+    that the network does not have raises a RuntimeError that names the key; entries of other networks are not looked at."""
+    prefix = "transformer_net."
+    want = dict(transformer_entries())
+    for key in state_dict:
+        if key.startswith(prefix) and key[len(prefix):] not in want:
+            raise RuntimeError(f"checkpoint entry '{key}' is no part of the transformer head (4 layers of width {MT_DIM})")
+    net = {}
+    for name, shape in want.items():
+        key = prefix + name
+        if key not in state_dict:
+            raise RuntimeError(f"checkpoint entry '{key}' is missing")
+        t = torch.as_tensor(state_dict[key])
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"checkpoint entry '{key}' has shape {tuple(t.shape)}, the transformer head needs {shape}")
+        net[name] = t.detach().to("cpu", torch.float32).contiguous()
+    return net
+
+
+def random_transformer():
+    """The network with torch's default initialisation of the reference's modules (random_init=True)."""
+    emb = torch.nn.Linear(MT_INPUTS, MT_DIM)
+    net = {"cls_token": torch.randn(1, 1, MT_DIM), "patch_embed.1.weight": emb.weight, "patch_embed.1.bias": emb.bias}
+    for l in range(MT_LAYERS):
+        layer = torch.nn.TransformerEncoderLayer(d_model=MT_DIM, nhead=MT_HEADS, dim_feedforward=MT_FF, activation="gelu", batch_first=True,
+                                                 norm_first=True)
+        net.update({f"transformer.layers.{l}.{k}": v for k, v in layer.state_dict().items()})
+    norm, lin = torch.nn.LayerNorm(MT_DIM), torch.nn.Linear(MT_DIM, 1)
+    net.update({"reg_head.0.weight": norm.weight, "reg_head.0.bias": norm.bias, "reg_head.1.weight": lin.weight, "reg_head.1.bias": lin.bias})
+    return transformer_from_state_dict({"transformer_net." + k: v.detach().clone() for k, v in net.items()})
+
+
+def _mt_layout():
+    """[(key, float offset, transposed)] of the packed buffer cvvdp_ml_transformer_head documents."""
+    D, FF = MT_DIM, MT_FF
+    out = [("cls_token", 0, False), ("patch_embed.1.weight", D, True), ("patch_embed.1.bias", D + MT_INPUTS * D, False)]
+    pos = 2 * D + MT_INPUTS * D
+    for l in range(MT_LAYERS):
+        p = f"transformer.layers.{l}."
+        for name, n, tr in (("norm1.weight", D, False), ("norm1.bias", D, False), ("self_attn.in_proj_weight", 3 * D * D, True),
+                            ("self_attn.in_proj_bias", 3 * D, False), ("self_attn.out_proj.weight", D * D, True),
+                            ("self_attn.out_proj.bias", D, False), ("norm2.weight", D, False), ("norm2.bias", D, False),
+                            ("linear1.weight", D * FF, True), ("linear1.bias", FF, False), ("linear2.weight", FF * D, True),
+                            ("linear2.bias", D, False)):
+            out.append((p + name, pos, tr))
+            pos += n
+    for name, n in (("reg_head.0.weight", D), ("reg_head.0.bias", D), ("reg_head.1.weight", D), ("reg_head.1.bias", 1)):
+        out.append((name, pos, False))
+        pos += n
+    assert pos + 3 == _capi.MT_WEIGHTS
+    return out
+
+
+def pack_transformer(net):
+    """float32 [MT_WEIGHTS]: every matrix transposed to [in][out], in the order cvvdp_ml_transformer_head documents."""
+    out = np.zeros(_capi.MT_WEIGHTS, dtype=f32)
+    for key, pos, tr in _mt_layout():
+        a = net[key].numpy()
+        a = np.ascontiguousarray(a.T if tr else a).reshape(-1)
+        out[pos:pos + a.size] = a
+    return out
+
+
+class cvvdp_ml_transformer(_cvvdp_ml):
+    """ColorVideoVDP-ML-Transformer.  `patch_size` and `dim` are the reference's constructor arguments, which its network does not
+    use beyond storing them; the kernels are written for dim = 256."""
+    _MODEL, _TITLE = "cvvdp_ml_transformer", "cvvdp-ml-transformer"
+    _WHERE = ("Pass the directory that holds the reference's cvvdp_ml_transformer/cvvdp_parameters.json and its cvvdp.ckpt as "
+              "config_paths=[dir]: this package ships neither file.")
+    _random_nets = staticmethod(random_transformer)
+    _nets_from_state_dict = staticmethod(transformer_from_state_dict)
+
+    def __init__(self, patch_size=(9, 16), dim=256, config_paths=[], **kwargs):
+        if dim != MT_DIM:
+            raise ValueError(f"cvvdp_ml_transformer: dim = {dim}, the model and its kernels are {MT_DIM} wide")
+        self.patch_size = patch_size
+        super().__init__(config_paths=config_paths, **kwargs)
+
+    def _set_nets(self, net):
+        self._nets = net
+        self._packed = pack_transformer(net)
+        self._weights_dev = None
+
+    def load_state_dict_nets(self, state_dict):
+        """Replace the network from a state dict with the 55 `transformer_net.*` entries; validated like a checkpoint, and nothing
+        changes if it does not validate."""
+        self._set_nets(transformer_from_state_dict(state_dict))
+
+    def state_dict_nets(self):
+        """The network as a state dict with the reference's keys (`transformer_net.cls_token`, ...)."""
+        return {"transformer_net." + k: t.clone() for k, t in self._nets.items()}
+
+    def packed_weights(self):
+        """float32 [MT_WEIGHTS]: the buffer the kernels read (pack_transformer)."""
+        return self._packed.copy()
+
+    def do_pooling_and_jods(self, features, return_y=False):
+        """cvvdp_ml_transformer.do_pooling_and_jods (cvvdp_ml_metric.py:647-675): features[band] is [B, F, H', W', C, 6] (any list of
+        such tensors; C = 3 marks an image) -> Q_JOD[B] on the device.  One cvvdp_ml_transformer_head call per band; unlike the
+        reference's, this one leaves the caller's tensors as they are.  With return_y also the list of y [B, F] per band, the
+        head's output per (item, frame) before the mean."""
+        B, C, bands = self._check_features(features)
+        if self._weights_dev is None:
+            self._weights_dev = torch.from_numpy(self._packed).to(self.device)
+        mask = sum(1 << s for s in set(self.disabled_features or ()))
+        lib = _capi.lib()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        ys = []
+        with torch.cuda.device(self.device):
+            Q = torch.full((B,), 10.0, dtype=torch.float32, device=self.device)
+            for f, scale in bands:
+                _, F, Hc, Wc = (int(n) for n in f.shape[:4])
+                nbytes = lib.cvvdp_ml_transformer_head_scratch_bytes(B, F, Hc, Wc)
+                scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+                y = torch.empty((B, F), dtype=torch.float32, device=self.device) if return_y else None
+                rc = lib.cvvdp_ml_transformer_head(self._handle, f.data_ptr(), B, F, Hc, Wc, C, self._weights_dev.data_ptr(), scale, mask,
+                                                   Q.data_ptr(), y.data_ptr() if return_y else None, scratch.data_ptr(), nbytes, stream)
+                _capi.check(self._handle, rc, "cvvdp_ml_transformer_head")
+                ys.append(y)
+        return (Q, ys) if return_y else Q
+
+    def full_name(self):
+        return "ColorVideoVDP-ML-Transformer"
+
+
+# (not registered: the -m choices of the command line come from the registry, and this metric is not on the command line yet)

@@ -423,6 +423,44 @@ int cvvdp_ml_saliency_head(cvvdp_handle* h, const float* dev_features, int32_t B
                            const float* dev_weights, float scale, uint32_t disabled_mask, float* dev_q, void* dev_scratch,
                            size_t scratch_bytes, void* stream);
 
+/* Head of the cvvdp-ml-transformer metric (cvvdp_ml_transformer.do_pooling_and_jods, pycvvdp/cvvdp_ml_metric.py:553-678) for ONE band of
+ * the features cvvdp_get_features delivers (dev_features as for cvvdp_ml_saliency_head, but 4-byte alignment is enough: fp32
+ * [B][F][Hc][Wc][C][6], C = 4 for a video, C = 3 for an image; only read).  Every (batch item, frame) is a sequence of N = Hc * Wc + 1
+ * tokens of 256 floats:
+ *   token 0 is cls_token; token 1 + cell is Linear(24 -> 256) of the cell's inputs: the variances become sqrt(|v|), statistic s of every
+ *   channel is 0 where bit s of disabled_mask is set, an image's fourth channel is 0; input c * 4 + s is statistic s < 4 of channel c,
+ *   input 16 + c * 2 + (s - 4) statistic s >= 4;
+ *   four encoder layers x += out_proj(MHA(LN1(x))), x += linear2(gelu(linear1(LN2(x)))): 8 heads of 32, softmax(q k' / sqrt(32)) over all
+ *   N keys, feed-forward 1024, the erf GELU, LayerNorm with biased variance and eps 1e-5, no final norm;
+ *   y[sequence] = relu(Linear(256 -> 1)(LayerNorm(x[token 0]))), written to dev_y (float [B * F]) unless that is null;
+ * and per batch item dev_q[b] = dev_q[b] - (mean of y over the item's F sequences) * scale in fp32: the caller fills dev_q (float [B])
+ * with 10, calls once per band, and scale is its product (1 / bands) * (baseband_weight on the last band) * (image_int for an image).
+ *   dev_weights   CVVDP_MT_WEIGHTS floats, 16-byte aligned; every matrix TRANSPOSED to [in][out] row-major, followed by its bias:
+ *                   float 0      cls_token [256]
+ *                   float 256    patch_embed.1: weight' [24][256], bias [256]
+ *                   float 6656   layer l at 6656 + l * 789760: norm1 weight [256], bias [256]; in_proj weight' [256][768], bias [768];
+ *                                out_proj weight' [256][256], bias [256]; norm2 weight [256], bias [256]; linear1 weight' [256][1024],
+ *                                bias [1024]; linear2 weight' [1024][256], bias [256]
+ *                   float 3165696  reg_head.0 weight [256], bias [256]; reg_head.1 weight [256], bias [1]; three floats of padding
+ *   dev_scratch   the scratch size function's bytes for (B, F, Hc, Wc), 16-byte aligned: B * F floats of y (rounded up to four) and
+ *                 1538 floats per token (x, the attention's output, q|k|v or the hidden layer, the LayerNorm statistics) and 1794 per
+ *                 sequence (the last layer's cls row) of one chunk of sequences.  Sequences are independent and are worked
+ *                 through in chunks of floor(CVVDP_MT_CHUNK_TOKENS / N) sequences (at least one), so the scratch does not grow with F
+ *                 beyond that.
+ * fp32 throughout; the matrix products are v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 accumulator: a k-ordered chain of fmaf), the
+ * softmax runs over tiles of 32 keys with a running maximum and sum, so no N x N matrix is stored.  The F values of an item are added in
+ * sequence order in double.  No atomics: every call gives the same bits, and the launch geometry depends on the shape alone.  Invalid
+ * arguments (C not 3 or 4, a null pointer other than dev_y, a size below 1, more than 2^31 - 1 tokens, a short or misaligned scratch)
+ * give CVVDP_E_ARG before any launch.  Needs no configured clip and touches no handle state (the handle carries the error text).
+ * Added; nothing else changed, so CVVDP_ABI_VERSION stays 14. */
+#define CVVDP_MT_WEIGHTS 3166468
+#define CVVDP_MT_CHUNK_TOKENS 32768
+size_t cvvdp_ml_transformer_head_scratch_bytes(int32_t B, int32_t F, int32_t Hc, int32_t Wc);
+int cvvdp_ml_transformer_head(cvvdp_handle* h, const float* dev_features, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C,
+                              const float* dev_weights, float scale, uint32_t disabled_mask, float* dev_q,
+                              float* dev_y /* may be null: float [B*F], y per sequence before the mean */,
+                              void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
