@@ -13,6 +13,8 @@ import functools
 import numpy as np
 import pytest
 
+from band_reference import fuse_clip as _clip, max_rel as _max_rel
+
 STRIP = 240                # columns of a strip (band4s.hip S_SW)
 FRAMES = 3
 
@@ -22,20 +24,6 @@ SHAPES = [
     (488, 98, "standard_4k"),       # W = 240 k + 248: the lane of columns W-4 .. W-1 is lane 63 of strip 1, where the shift hands in 0
     (960, 400, "standard_fhd"),     # two row segments, two border-free strips side by side (a seam between two k_band4s blocks)
 ]
-
-
-def _clip(W, H, F, seed):           # (test_gpu_parity.py _fuse_clip)
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:H, 0:W]
-    ref = np.stack([np.stack([0.45 + 0.3 * np.sin(2 * np.pi * (3.1 * x / W + f / 9.0) + c) * np.cos(2 * np.pi * 2.3 * y / H) for c in range(3)])
-                    for f in range(F)], axis=1)[None]
-    test = np.clip(ref + 0.05 * rng.standard_normal(ref.shape), 0, 1)
-    return np.round(test * 255).astype(np.uint8), np.round(ref * 255).astype(np.uint8)
-
-
-def _max_rel(a, b):
-    nz = b != 0
-    return float(np.max(np.abs(a[nz] - b[nz]) / np.abs(b[nz]))) if nz.any() else 0.0
 
 
 @pytest.mark.parametrize("W,H,disp", SHAPES)

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from band_reference import fuse_clip as _clip, max_rel as _max_rel
+
 pytestmark = pytest.mark.gpu
 
 MIN_EVEN_H, MIN_ODD_H = 32, 33        # the smallest heights the fused route takes
@@ -23,20 +25,6 @@ SHAPES = [
     (964, 386, 2, "standard_fhd"),           # segment boundaries at an odd distance from the top mirror
     (1446, 333, 2, "standard_hdr_pq"),       # W % 4 == 2: the border strips run k_band4f beside the changed kernel; odd height
 ]
-
-
-def _max_rel(a, b):
-    nz = b != 0
-    return float(np.max(np.abs(a[nz] - b[nz]) / np.abs(b[nz]))) if nz.any() else 0.0
-
-
-def _clip(W, H, F, seed):
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:H, 0:W]
-    ref = np.stack([np.stack([0.45 + 0.3 * np.sin(2 * np.pi * (3.1 * x / W + f / 9.0) + c) * np.cos(2 * np.pi * 2.3 * y / H) for c in range(3)])
-                    for f in range(F)], axis=1)[None]
-    test = np.clip(ref + 0.05 * rng.standard_normal(ref.shape), 0, 1)
-    return np.round(test * 255).astype(np.uint8), np.round(ref * 255).astype(np.uint8)
 
 
 @pytest.mark.parametrize("W,H,F,disp", SHAPES)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from band_reference import fuse_clip as _fuse_clip      # the clip of every fused-kernel test: one definition
 from conftest import golden_cases, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +99,8 @@ def test_block_size_invariance(name, block):
 
 def test_intermediates_against_oracle():
     """Ring (DKL), temporal channels, Gaussian pyramid and per-pixel D of every band vs the CPU oracle.
-    (The first stage alone, every frame, route and sample format against float64: test_fir_probe_gpu.py.)"""
+    (The first stage alone, every frame, route and sample format against float64: test_fir_probe_gpu.py.  The band stage on every
+    route, per pixel at every frame and shape and through localized differences, against float64: test_band_probe_gpu.py.)"""
     from colorvideovdp_amd import _capi
     from oracle import cvvdp_oracle as orc
     g = load_golden("vid_u8_72x128x12_60_fhd")
@@ -1221,15 +1223,6 @@ def test_fused_features_on_ragged_multi_strip_frames(W, H, F, disp, fuse_mode):
 # k_band4f (band4f.hip): band kernels that compute the next pyramid level themselves.  Normal use picks them per clip for blocks that
 # fill the GPU several times over (the bench clips: test_bench_clip_against_reference holds them to the real reference); here the
 # test hook cvvdp.fuse_mode forces them on small frames, where the oracle is affordable and every border rule is close by.
-def _fuse_clip(W, H, F, seed):
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:H, 0:W]
-    ref = np.stack([np.stack([0.45 + 0.3 * np.sin(2 * np.pi * (3.1 * x / W + f / 9.0) + c) * np.cos(2 * np.pi * 2.3 * y / H) for c in range(3)])
-                    for f in range(F)], axis=1)[None]
-    test = np.clip(ref + 0.05 * rng.standard_normal(ref.shape), 0, 1)
-    return np.round(test * 255).astype(np.uint8), np.round(ref * 255).astype(np.uint8)
-
-
 @pytest.mark.parametrize("W,H,F,fps,disp", [
     (256, 144, 5, 30, "standard_fhd"),        # one strip, levels 256x144 -> 128x72 -> 64x36 fused
     (736, 416, 3, 60, "standard_4k"),         # four strips (the last one narrow), several segments
