@@ -17,7 +17,7 @@ RESIZE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2, "area": 3}   # CVVDP_
 
 U8, U16, F16, F32, F32_DKL, YUV8, YUV16 = range(7)
 HEATMAP = {None: 0, "none": 0, "raw": 1, "threshold": 2, "supra-threshold": 3}
-BUF_HIST, BUF_GPYR, BUF_DDUMP, BUF_HEAT, BUF_Q = range(5)
+BUF_HIST, BUF_GPYR, BUF_DDUMP, BUF_HEAT, BUF_Q, BUF_HSTATS, BUF_HCURVE = range(7)
 
 
 class Params(C.Structure):

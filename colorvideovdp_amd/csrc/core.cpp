@@ -1387,6 +1387,12 @@ int cvvdp_debug_buffer(cvvdp_handle* h, int32_t which, int32_t level, void** dev
     case CVVDP_BUF_HEAT:
       if (h->c.heatmap == CVVDP_HEATMAP_NONE) return fail(h, CVVDP_E_STATE, "heat map not enabled");
       *dev_ptr = h->ws + lv.heat_off; *n_floats = (size_t)h->items_cap_s * lv.P; break;
+    case CVVDP_BUF_HSTATS:
+    case CVVDP_BUF_HCURVE:
+      if (h->c.heatmap == CVVDP_HEATMAP_NONE || h->c.heatmap == CVVDP_HEATMAP_RAW) return fail(h, CVVDP_E_STATE, "no tone-mapping statistics without a colour-mapped heat map");
+      if (which == CVVDP_BUF_HSTATS) { *dev_ptr = h->ws + h->hstats_off; *n_floats = (size_t)h->last_items * kHeatStatsWords; }
+      else { *dev_ptr = h->ws + h->hcurve_off; *n_floats = (size_t)h->last_items * kHeatCurveWords; }
+      break;
     case CVVDP_BUF_Q: *dev_ptr = h->ws + h->q_off; *n_floats = (size_t)h->c.batch * h->nch * h->c.n_frames * h->L; break;
     default: return fail(h, CVVDP_E_ARG, "unknown buffer");
   }

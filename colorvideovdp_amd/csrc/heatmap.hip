@@ -179,16 +179,19 @@ __global__ __launch_bounds__(256) void k_heat_curve(HeatArgs a) {
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
   if ((t & 63) == 0) s_tmp[t >> 6] = part;
   __syncthreads();
-  // p^(1/3) / sum: element-wise, by every thread; the running sum stays one thread's in-order chain (1024 dependent additions, as the
-  // reference's cumsum) -- with the 1024 IEEE divisions inside that chain the kernel took 55 us per launch (round 6b)
+  // p^(1/3) / sum: element-wise, by every thread; the running sum stays one thread's in-order chain (1024 dependent additions)
+  // -- with the 1024 IEEE divisions inside that chain the kernel took 55 us per launch (round 6b).  The chain runs in DOUBLE and
+  // every node is rounded to float once: that is the reference's cumsum (torch's CPU cumsum accumulates float in double; its result
+  // is the rounded float64 sum, bit for bit).  As an fp32 chain the curve was up to 4e-6 off the curve of its own counts
+  // (tests/test_heat_probe_gpu.py), ten times the reference's own error.
   const float tot = s_tmp[0] + s_tmp[1] + s_tmp[2] + s_tmp[3];
   for (int i = t; i < 1024; i += 256) s_p[i] = s_p[i] / tot;
   __syncthreads();
   if (t == 0) {
-    float run = 0.0f;
+    double run = 0.0;
     for (int i = 0; i < 1024; ++i) {
-      run += s_p[i];
-      s_p[i] = run;
+      run += (double)s_p[i];
+      s_p[i] = (float)run;
     }
   }
   __syncthreads();

@@ -67,7 +67,7 @@ enum { CVVDP_EOTF_SRGB = 0, CVVDP_EOTF_PQ = 1, CVVDP_EOTF_HLG = 2, CVVDP_EOTF_LI
 /* heat-map modes, cvvdp_metric.py:117 */
 enum { CVVDP_HEATMAP_NONE = 0, CVVDP_HEATMAP_RAW = 1, CVVDP_HEATMAP_THRESHOLD = 2, CVVDP_HEATMAP_SUPRA = 3 };
 /* debug/inspection buffers inside the workspace (tests) */
-enum { CVVDP_BUF_HIST = 0, CVVDP_BUF_GPYR = 1, CVVDP_BUF_DDUMP = 2, CVVDP_BUF_HEAT = 3, CVVDP_BUF_Q = 4 };
+enum { CVVDP_BUF_HIST = 0, CVVDP_BUF_GPYR = 1, CVVDP_BUF_DDUMP = 2, CVVDP_BUF_HEAT = 3, CVVDP_BUF_Q = 4, CVVDP_BUF_HSTATS = 5, CVVDP_BUF_HCURVE = 6 };
 
 /* Calibrated parameters + display photometry.  Host-side scalars of cvvdp_parameters.json as
  * loaded by cvvdp.load_config (cvvdp_metric.py:146-229) and of vvdp_display_photo_eotf
@@ -568,7 +568,12 @@ int cvvdp_get_heatmap_rgb8(cvvdp_handle* h, int32_t n_frames, void* dev_out_u8, 
 /* Test/inspection: device pointer + element count of an internal buffer (level where relevant).  CVVDP_BUF_HEAT: level l holds the
  * heat-map reconstruction from the coarsest level up to l (lpyr_dec.py:328-335) -- EXCEPT level 0 of frames with at least two pyramid
  * levels and W % 4 == 0: there the last step (level 1 -> 0) is done inside the finishing kernels (cvvdp_get_heatmap*), so level 0 holds
- * the bare level-0 band and the full reconstruction never exists as a plane. */
+ * the bare level-0 band and the full reconstruction never exists as a plane.
+ * CVVDP_BUF_HSTATS / CVVDP_BUF_HCURVE (colour-mapped heat maps only, CVVDP_E_STATE otherwise; the level is ignored): what the last
+ * cvvdp_get_heatmap* call left of the tone mapping, per item of the last block.  HSTATS: 4 + 1024 32-bit words per item -- [0] the bits
+ * of the smallest positive sample of the context plane, [1] the bits of its largest sample, [2], [3] unused, [4 ..) the 1024 histogram
+ * counts (unsigned integers; n_floats counts words).  HCURVE: 1024 + 4 floats per item -- the tone curve's 1024 values, [1024] b_min,
+ * [1025] b_max, [1026] 1 for the histogram curve or 0 for the linear one (b_max - b_min < 0.6), [1027] unused. */
 int cvvdp_debug_buffer(cvvdp_handle* h, int32_t which, int32_t level, void** dev_ptr, size_t* n_floats);
 
 /* Profiling aid for bench.py: when enabled, the core brackets every kernel launch with hipEvents on

@@ -47,8 +47,10 @@ def _release(m):
 
 def _check_heatmap(got, want, name=None):
     """Generic bound: <= 1e-3 of the pixels off by more than 2e-3, none by more than 2e-2 (~20 fp16 ulp near 1).  Fixtures with a
-    recorded margin (conftest.observed_bound) are held to 1.5 x what this build was observed to do on them -- a one-bin shift of the
-    tone-map histogram (visualize_diff_map.py:26-35) moves thousands of pixels and cannot hide in the generic bound then."""
+    recorded margin (conftest.observed_bound) are held to 1.5 x what this build was observed to do on them.  This is an end-to-end
+    bound over whole frames: one wrong column, a tile seam or a tone-curve value from the neighbouring node fit inside it.  What holds
+    the heat-map kernels per pixel and per stage (reconstruction, range, histogram bins, tone curve, colour map) is
+    test_heat_probe_gpu.py, against the float64 heat_reference.py."""
     from conftest import observed_bound, record_observed
     got = got.numpy().astype(np.float32) if torch.is_tensor(got) else np.asarray(got, dtype=np.float32)
     want = np.asarray(want).astype(np.float32)
