@@ -74,6 +74,7 @@ struct cvvdp_handle {
   hipEvent_t ev_edge_fork[3] = {nullptr, nullptr, nullptr}, ev_edge_join[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_reduce[2] = {nullptr, nullptr}, ev_band[2] = {nullptr, nullptr};
   bool band_pending[2] = {false, false};
+  bool image_put = false, image_scored = false;   // image clips: cvvdp_put_image / cvvdp_process_image have run since cvvdp_configure (cvvdp_image_gradient)
 };
 
 namespace {
@@ -617,6 +618,7 @@ int cvvdp_configure(cvvdp_handle* h, const cvvdp_clip* clip) {
   h->ws = nullptr;
   h->configured = true;
   h->last_items = 0; h->last_item0 = 0; h->last_q0 = 0;
+  h->image_put = h->image_scored = false;
   return CVVDP_OK;
 }
 
@@ -714,7 +716,10 @@ int cvvdp_put_image(cvvdp_handle* h, const void* t, const void* r, int32_t dtype
     ProfScope ps(h, CVVDP_PROF_PHOTOMETRY, s);
     launch_photometry(a, s);
   }
-  return check_launch(h, "photometry");
+  h->image_scored = false;
+  const int rc = check_launch(h, "photometry");
+  h->image_put = rc == CVVDP_OK;
+  return rc;
 }
 
 static int process_block_impl(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
@@ -984,6 +989,113 @@ int cvvdp::mt_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_
   return CVVDP_OK;
 }
 int cvvdp::mt_head_check_launch(cvvdp_handle* h) { return check_launch(h, "ml_transformer_head"); }
+// cvvdp_image_gradient (grad.hip) up to the launches.  The caller's scratch, in floats, every part on a 256-byte granule:
+// coef [B][3][L]; three temporaries [3][B][P0]; per level d [3][B][P_l] and (all but the baseband) ey [B][P_l]
+namespace {
+struct GradLayout { size_t coef, t[3], d[CVVDP_MAX_LEVELS], ey[CVVDP_MAX_LEVELS], total; };
+bool grad_clip_ok(const cvvdp_handle* h) { return h && h->configured && !h->c.is_video && h->c.channels == 3; }
+GradLayout grad_layout(const cvvdp_handle* h) {
+  GradLayout g{};
+  const size_t B = (size_t)h->c.batch;
+  size_t off = 0;
+  g.coef = off; off += align_up(B * 3 * h->L);
+  for (int k = 0; k < 3; ++k) { g.t[k] = off; off += align_up(3 * B * (size_t)h->lv[0].P); }
+  for (int l = 0; l < h->L; ++l) {
+    g.d[l] = off; off += align_up(3 * B * (size_t)h->lv[l].P);
+    g.ey[l] = off; if (l + 1 < h->L) off += align_up(B * (size_t)h->lv[l].P);
+  }
+  g.total = off;
+  return g;
+}
+}  // namespace
+size_t cvvdp::grad_scratch(const cvvdp_handle* h) { return grad_clip_ok(h) ? grad_layout(h).total * sizeof(float) : 0; }
+int cvvdp::grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
+                        size_t scratch_bytes, GradPlan& plan) {
+  if (!h) return CVVDP_E_STATE;
+  if (!test || !st || !grad || !sg || !scratch) return fail(h, CVVDP_E_ARG, "image_gradient: null argument");
+  if (reinterpret_cast<uintptr_t>(test) % 4 || reinterpret_cast<uintptr_t>(grad) % 4 || reinterpret_cast<uintptr_t>(scratch) % 16)
+    return fail(h, CVVDP_E_ARG, "image_gradient: test and gradient must be 4-byte aligned, the scratch 16-byte aligned");
+  if (!h->configured) return fail(h, CVVDP_E_STATE, "image_gradient: configure first");
+  const cvvdp_clip& c = h->c;
+  if (c.is_video) return fail(h, CVVDP_E_STATE, "image_gradient: configured for video; the gradient exists for images only");
+  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: 1-channel content is out of scope");
+  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: not with a heat map or features");
+  if (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG)
+    return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)");
+  if (c.batch > 21845) return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: batch of %d too large", c.batch);   // (3 planes per item in a grid's y)
+  const int B = c.batch, L = h->L, H = c.height, W = c.width;
+  // the gradient's extent: the last element written is sum (size - 1) * stride over B, C, H, W
+  {
+    const int64_t dims[5] = {B, 3, 1, H, W};
+    int64_t last = 0, term = 0;
+    bool bad = false;
+    for (int k = 0; k < 5 && !bad; ++k) {
+      if (k == 2) continue;
+      bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
+    }
+    if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
+      return fail(h, CVVDP_E_ARG, "image_gradient: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d samples at these strides", grad_bytes, B, H, W);
+  }
+  const GradLayout lay = grad_layout(h);
+  if (scratch_bytes < lay.total * sizeof(float))
+    return fail(h, CVVDP_E_ARG, "image_gradient: scratch of %zu bytes, %zu needed", scratch_bytes, lay.total * sizeof(float));
+  if (!h->ws || !h->image_scored) return fail(h, CVVDP_E_STATE, "image_gradient: valid after cvvdp_put_image and cvvdp_process_image");
+  float* sc = static_cast<float*>(scratch);
+  const float K[5] = {kGaussK0, 0.25f, 0.4f, 0.25f, kGaussK0};
+  plan = GradPlan{};
+  plan.L = L;
+  GradPoolArgs& po = plan.pool;
+  po.q = h->ws + h->q_off; po.coef = sc + lay.coef; po.B = B; po.L = L;
+  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
+  for (int k = 0; k < 3; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
+  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp; po.image_int = h->p.image_int;
+  for (int l = 0; l + 1 < L; ++l) {
+    const Level& lv = h->lv[l];
+    const Level& lc = h->lv[l + 1];
+    GradBandArgs& a = plan.band[l];
+    a.g = gbase(h, l, 0); a.gps = (int64_t)level_cap(h, l) * lv.P;
+    a.gc = gbase(h, l + 1, 0); a.gcps = (int64_t)h->items_cap_s * lc.P;
+    a.H = lv.H; a.W = lv.W; a.Hc = lc.H; a.Wc = lc.W; a.B = B; a.blur = lv.blur; a.level = l; a.L = L;
+    a.band_mul = l == 0 ? 1.0f : 2.0f;
+    std::memcpy(a.lut, h->c.csf_rows + (size_t)l * 4 * CVVDP_CSF_NODES, sizeof a.lut);
+    a.logL_first = h->p.csf_logL_first; a.logL_last = h->p.csf_logL_last; a.sens_mul = h->p.sens_mul;
+    for (int k = 0; k < 3; ++k) {
+      a.ch_gain[k] = h->p.ch_gain[k]; a.q[k] = h->p.mask_q[k]; a.eps_q[k] = std::pow(kEps, h->p.mask_q[k]);
+      for (int j = 0; j < 3; ++j) a.xw[k * 3 + j] = h->p.xcm[k * 4 + j];
+    }
+    a.mask_c10 = h->p.mask_c10; a.mask_p = h->p.mask_p; a.eps_p = std::pow(kEps, h->p.mask_p); a.dmax = h->p.d_max10;
+    a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
+    for (int k = 0; k < 13; ++k) a.taps[k] = h->p.blur_taps[k];
+    a.coef = po.coef;
+    a.t0 = sc + lay.t[0]; a.t1 = sc + lay.t[1]; a.t2 = sc + lay.t[2];
+    a.d = sc + lay.d[l]; a.ey = sc + lay.ey[l];
+  }
+  {
+    const Level& lv = h->lv[L - 1];
+    GradBaseArgs& b = plan.base;
+    b.g = gbase(h, L - 1, 0); b.gps = (int64_t)level_cap(h, L - 1) * lv.P;
+    b.H = lv.H; b.W = lv.W; b.B = B; b.level = L - 1; b.L = L;
+    std::memcpy(b.lut, h->c.csf_rows + (size_t)(L - 1) * 4 * CVVDP_CSF_NODES, sizeof b.lut);
+    b.logL_first = h->p.csf_logL_first; b.logL_last = h->p.csf_logL_last; b.sens_mul = h->p.sens_mul;
+    b.coef = po.coef; b.d = sc + lay.d[L - 1];
+  }
+  for (int l = 0; l < L; ++l) {
+    GradAccumArgs& a = plan.acc[l];
+    a.d = sc + lay.d[l]; a.H = h->lv[l].H; a.W = h->lv[l].W; a.B = B;
+    if (l > 0) { a.d_f = sc + lay.d[l - 1]; a.ey_f = sc + lay.ey[l - 1]; a.Hf = h->lv[l - 1].H; a.Wf = h->lv[l - 1].W; }
+    if (l + 1 < L) { a.tot_c = sc + lay.d[l + 1]; a.Hc = h->lv[l + 1].H; a.Wc = h->lv[l + 1].W; }
+    a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
+    for (int k = 0; k < 5; ++k) a.K[k] = K[k];
+  }
+  GradDisplayArgs& d = plan.dsp;
+  d.tot = sc + lay.d[0];
+  d.test = static_cast<const float*>(test); d.tb = st[0]; d.tc = st[1]; d.th = st[3]; d.tw = st[4];
+  d.grad = grad; d.gb = sg[0]; d.gc = sg[1]; d.gh = sg[3]; d.gw = sg[4];
+  d.H = H; d.W = W; d.B = B;
+  fill_display(h, d.dm);
+  return CVVDP_OK;
+}
+int cvvdp::grad_check_launch(cvvdp_handle* h) { return check_launch(h, "image_gradient"); }
 // cvvdp_pixel_preview (preview.hip) up to the launch: the source checks of cvvdp_pixel_sse on one side, then the target, the format and
 // the canvas.  Nothing is launched unless the last pixel of the last frame lies inside dst_bytes.
 int cvvdp::preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref,
@@ -1292,7 +1404,9 @@ int cvvdp_get_features(cvvdp_handle* h, int32_t band, int32_t n_frames, float* d
 int cvvdp_process_image(cvvdp_handle* h, void* stream) {
   if (!h || !h->ws) return fail(h, CVVDP_E_STATE, "no workspace bound");
   if (h->c.is_video) return fail(h, CVVDP_E_STATE, "configured for video");
-  return run_pyramid_and_bands(h, 1, 0, static_cast<hipStream_t>(stream));
+  const int rc = run_pyramid_and_bands(h, 1, 0, static_cast<hipStream_t>(stream));
+  h->image_scored = rc == CVVDP_OK && h->image_put;
+  return rc;
 }
 
 int cvvdp_get_q_per_ch(cvvdp_handle* h, float* dev_out, void* stream) {

@@ -597,4 +597,73 @@ int mt_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, in
 int mt_head_check_launch(cvvdp_handle* h);
 void launch_mt_head(const MtHeadArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- gradient of the image JOD (grad.hip, grad_dev.h)
+// d JOD[b] / d test[b] of the image scored last, walked backwards through the graph of the forward.  Every kernel is a
+// gather: one thread per output element, no atomics.  Three channels, one item per batch entry; forward planes come from the workspace
+// (plane 2 c = test, 2 c + 1 = reference of channel c; kept for every level by the image route), everything else from the caller's scratch.
+struct GradPoolArgs {        // dJOD/dQ_per_ch, folded with the derivative of the spatial norm (grad_dev.h g_pool_coef)
+  const float* q;           // Q_per_ch [B][3][L]
+  float* coef;              // [B][3][L]
+  int32_t B, L;
+  int32_t n_px[CVVDP_MAX_LEVELS];
+  float ch_w[3], bb_w[3];
+  float beta_sch, beta_tch, jod_a, jod_exp, image_int;
+};
+struct GradBandArgs {        // one Laplacian level
+  const float* g;  int64_t gps;     // level l: plane p of item i at g + p * gps + i * H * W
+  const float* gc; int64_t gcps;    // level l + 1
+  int32_t H, W, Hc, Wc, B, blur;
+  int32_t level, L;
+  float band_mul;
+  float lut[3 * CVVDP_CSF_NODES];
+  float logL_first, logL_last, sens_mul;
+  float ch_gain[3], q[3], eps_q[3];
+  float mask_c10, mask_p, eps_p, dmax;
+  float xw[9];               // [k][c]: weight of channel k's mask in channel c
+  float kx[3];               // expand taps (BandArgs.kx)
+  float taps[13];
+  const float* coef;         // [B][3][L]
+  float *t0, *t1, *t2;       // temporaries, [3][B][H * W] each
+  float* d;                  // out: dJOD/d(layer) [3][B][H * W]
+  float* ey;                 // out: dJOD/d(expanded test Y) [B][H * W]
+};
+struct GradBaseArgs {        // the baseband
+  const float* g; int64_t gps;
+  int32_t H, W, B, level, L;
+  float lut[3 * CVVDP_CSF_NODES];
+  float logL_first, logL_last, sens_mul;
+  const float* coef;
+  float* d;                  // out: dJOD/dg [3][B][H * W]
+};
+struct GradAccumArgs {       // level l: d (direct) -> total, in place; coarsest level first
+  float* d;                  // [3][B][H * W]
+  const float* d_f;          // finer level's d [3][B][Hf * Wf] (still its direct part) and ey [B][Hf * Wf], or null at level 0
+  const float* ey_f;
+  const float* tot_c;        // coarser level's total [3][B][Hc * Wc], or null at the last level
+  int32_t H, W, Hf, Wf, Hc, Wc, B;
+  float kx[3], K[5];
+};
+struct GradDisplayArgs {     // total of level 0 -> dJOD/dV, written through the caller's strides
+  const float* tot;          // [3][B][H * W]
+  const float* test; int64_t tb, tc, th, tw;
+  float* grad; int64_t gb, gc, gh, gw;
+  int32_t H, W, B;
+  DisplayArgs dm;
+};
+struct GradPlan {            // everything cvvdp_image_gradient launches, filled by core.cpp
+  int32_t L;
+  GradPoolArgs pool;
+  GradBandArgs band[CVVDP_MAX_LEVELS];      // levels 0 .. L - 2
+  GradBaseArgs base;
+  GradAccumArgs acc[CVVDP_MAX_LEVELS];
+  GradDisplayArgs dsp;
+};
+static_assert(sizeof(GradBandArgs) <= 4096 && sizeof(GradDisplayArgs) <= 4096, "kernel arguments of the gradient kernels");
+// core.cpp: scratch size of the configured clip (0: no gradient for it), argument / state checks and the plan; the error of a launch
+size_t grad_scratch(const cvvdp_handle* h);
+int grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
+                 size_t scratch_bytes, GradPlan& plan);
+int grad_check_launch(cvvdp_handle* h);
+void launch_image_gradient(const GradPlan& p, hipStream_t s);
+
 }  // namespace cvvdp

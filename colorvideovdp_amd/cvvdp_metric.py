@@ -8,7 +8,8 @@ pointers and mirrors the reference's host-side bookkeeping (temporal padding, st
 
 Differences that are deliberate:
   * GPU only.  There is no CPU path and no fallback: without the HIP library or a GPU the class raises.
-  * inference only.  `loss()` returns 10-JOD without autograd (the reference is differentiable).
+  * `loss()` returns 10-JOD without autograd and refuses inputs that require a gradient.  The gradient of an image's JOD with respect
+    to the test image comes from `predict_with_gradient()` / `differentiable_loss()` (HIP backward, csrc/grad.hip).
   * frames per block are chosen for occupancy / memory, never change results beyond fp32 rounding, and
     heat-map tone-mapping statistics are always per frame (the reference's CPU behaviour; on CUDA the
     reference lets them depend on the block size).
@@ -30,7 +31,7 @@ from ._frames import batch_strides, yuv_block_resized
 from .config import config_files, json2dict, load_config
 from .display_model import vvdp_display_geometry, vvdp_display_photo_eotf, vvdp_display_photometry
 from .sharding import all_gather_frames, plan_frame_shard
-from .video_source import video_source, video_source_array
+from .video_source import reshuffle_dims, video_source, video_source_array
 from .vq_metric import register_metric, vq_exception, vq_metric
 
 f32 = np.float32
@@ -261,6 +262,23 @@ class _DumpOut:
 
     def finish(self):
         self._deliver()
+
+
+class _JodLoss(torch.autograd.Function):
+    """10 - JOD with the gradient of cvvdp.predict_with_gradient (cvvdp.differentiable_loss)."""
+
+    @staticmethod
+    def forward(ctx, test, reference, metric, dim_order):
+        jod, grad = metric.predict_with_gradient(test, reference, dim_order)
+        ctx.save_for_backward(grad)
+        ctx.batch_shape = [n if ch == "B" else 1 for ch, n in zip(dim_order.upper(), grad.shape)]
+        return 10.0 - jod
+
+    @staticmethod
+    def backward(ctx, upstream):
+        grad, = ctx.saved_tensors
+        up = upstream if upstream.dim() == 0 else upstream.reshape(ctx.batch_shape)      # one factor per batch item
+        return -grad * up, None, None, None
 
 
 class cvvdp(vq_metric):
@@ -527,9 +545,73 @@ class cvvdp(vq_metric):
     def loss(self, test_cont, reference_cont, dim_order="BCFHW", frames_per_second=0):
         for a in (test_cont, reference_cont):
             if torch.is_tensor(a) and a.requires_grad:
-                raise vq_exception("colorvideovdp_amd is inference-only: loss() does not propagate gradients")
+                raise vq_exception("colorvideovdp_amd is inference-only: loss() does not propagate gradients "
+                                   "(differentiable_loss() does, for images)")
         Q_jod, _ = self.predict(test_cont, reference_cont, dim_order=dim_order, frames_per_second=frames_per_second)
         return 10.0 - Q_jod
+
+    def _gradient_inputs(self, test, reference, dim_order):
+        """What predict_with_gradient refuses, checked before anything touches the device; returns the BCFHW views."""
+        if not torch.is_tensor(test) or not torch.is_tensor(reference):
+            raise vq_exception("predict_with_gradient: test and reference must be torch tensors")
+        if test.dtype != torch.float32 or reference.dtype != torch.float32:
+            raise vq_exception("predict_with_gradient: integer and fp16 inputs are out of scope, test and reference must be float32")
+        if self.do_heatmap:
+            raise vq_exception("predict_with_gradient: not available with a heat map")
+        if self.dump_channels is not None:
+            raise vq_exception("predict_with_gradient: not available with dump_channels")
+        if len(dim_order) != test.dim() or len(dim_order) != reference.dim():
+            raise vq_exception('predict_with_gradient: the tensors must have as many dimensions as there are characters in "dim_order"')
+        t = reshuffle_dims(test.detach(), dim_order, "BCFHW")
+        r = reshuffle_dims(reference.detach(), dim_order, "BCFHW")
+        if t.shape[2] != 1 or r.shape[2] != 1:
+            raise vq_exception("predict_with_gradient: video is out of scope, the gradient exists for images (one frame) only")
+        if t.shape[1] != 3 or r.shape[1] != 3:
+            raise vq_exception("predict_with_gradient: 1-channel content is out of scope, the images must have three colour channels")
+        if tuple(t.shape[3:]) != tuple(r.shape[3:]) or (r.shape[0] != t.shape[0] and r.shape[0] != 1):
+            raise vq_exception("predict_with_gradient: the reference must have the test's shape (or a batch of 1)")
+        eotf, _ = self.display_photometry.eotf_params()
+        if eotf in (1, 2):      # CVVDP_EOTF_PQ, CVVDP_EOTF_HLG
+            raise vq_exception("predict_with_gradient: PQ and HLG displays are refused (the reference's own gradient is NaN as soon as a sample is 0)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
+        if t.device != self.device or r.device != self.device:
+            raise vq_exception(f"predict_with_gradient: test and reference must be tensors on {self.device}")
+        return t, r
+
+    def predict_with_gradient(self, test, reference, dim_order="BCFHW"):
+        """(jod, grad) of an image: `jod` as predict() returns it, `grad` = d jod / d test, float32 on the device, with the shape of
+        `test` in the caller's dim_order; for a batch, grad[b] is the gradient of jod[b] (items do not interact).  float32 tensors on the
+        metric's device, three channels, one frame; sRGB, numeric-gamma and linear displays.  Video, 1-channel content, other dtypes,
+        heat maps, dump_channels and PQ / HLG displays are refused with a vq_exception; there is no gradient for the reference.
+        The backward runs in HIP (cvvdp_image_gradient, csrc/grad.hip) on the pyramid the forward left in the workspace, with torch's
+        subgradient conventions, and gives the same bits on every run.  Images are always scored on the core's unfused route (what
+        fuse_mode = 2 selects for video, as with dump_channels): the JOD is that of predict()."""
+        t, r = self._gradient_inputs(test, reference, dim_order)
+        vs = video_source_array(t, r, 0, dim_order="BCFHW", display_photometry=self.display_photometry)
+        Q, _, _ = self._score_range(vs, 0, 1)
+        jod = self.do_pooling_and_jods(Q)
+        lib = _capi.lib()
+        grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
+        gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
+        assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
+        need = lib.cvvdp_image_gradient_scratch_bytes(self._handle)
+        scratch = torch.empty(max(int(need), 16), dtype=torch.uint8, device=self.device)
+        st = (ctypes.c_int64 * 5)(*t.stride())
+        sg = (ctypes.c_int64 * 5)(*gv.stride())
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = lib.cvvdp_image_gradient(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(), scratch.numel(), stream)
+        _capi.check(self._handle, rc, "cvvdp_image_gradient")
+        del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
+        return jod.squeeze(), grad
+
+    def differentiable_loss(self, test, reference, dim_order="BCFHW"):
+        """10 - JOD of an image as a tensor attached to autograd (the reference's loss(): examples/ex_image_reconstruction.py runs with
+        this method's name in place of `loss`).  backward() multiplies the gradient predict_with_gradient() stored by the upstream
+        gradient; the reference receives None, and a reference that requires a gradient is refused."""
+        if torch.is_tensor(reference) and reference.requires_grad:
+            raise vq_exception("differentiable_loss: a gradient for the reference is out of scope")
+        return _JodLoss.apply(test, reference, self, dim_order)
 
     def predict_video_source(self, vid_source, heatmap_sink=None):
         """cvvdp_metric.py:304-441.

@@ -461,6 +461,27 @@ int cvvdp_ml_transformer_head(cvvdp_handle* h, const float* dev_features, int32_
                               float* dev_y /* may be null: float [B*F], y per sequence before the mean */,
                               void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* Gradient of the image JOD with respect to the TEST image: dev_grad[b] = d JOD[b] / d test[b] (the reference's cvvdp.loss(...).backward()
+ * gives the negative: its loss is 10 - JOD).  Valid after cvvdp_put_image and cvvdp_process_image on an image clip of three channels,
+ * configured without heat map and without features, on a display with the sRGB, a numeric-gamma or the linear EOTF; batch items do not
+ * interact.  The forward's Gaussian levels and Q_per_ch are read from the workspace, which must not have been touched since.
+ *   dev_test       the fp32 test samples cvvdp_put_image was given (dtype CVVDP_F32), with their element strides (B, C, F, H, W; F unused)
+ *   dev_grad       fp32, written through strides_grad (same order, every stride >= 0): B x 3 x H x W samples; the last one must lie inside
+ *                  grad_bytes
+ *   dev_scratch    cvvdp_image_gradient_scratch_bytes(h) bytes, 16-byte aligned (the size of the CONFIGURED clip: 0 for a video, a
+ *                  1-channel or an unconfigured clip).  About 14.3 floats per pixel and batch item: three temporaries of three planes,
+ *                  and per pyramid level three planes of d JOD / d g_l and one of d JOD / d expand(g_l+1)_Y
+ * The backward walks the forward's graph (display model, DKL, Gaussian pyramid, Weber contrast, mutual masking with the 13 x 13
+ * reflect-padded blur, soft clamp, spatial norm, pooling) with torch's subgradient conventions: abs'(0) = 0, clamp passes its gradient at
+ * the bound, min splits ties in half, sRGB takes the linear branch at p <= 0.04045; samples outside [0, 1] receive exactly 0.  Every
+ * kernel is a gather without atomics: the same bits on every run.  Nothing synchronises: d JOD / d Q_per_ch is computed by a kernel.
+ * Argument errors (null pointer, misaligned pointer, negative stride, short gradient buffer or scratch) give CVVDP_E_ARG, what is out of
+ * scope (1 channel, heat map, features, PQ / HLG) CVVDP_E_UNSUPPORTED, a video clip or a call before the image was scored CVVDP_E_STATE --
+ * all before any launch.  Added; nothing else changed, so CVVDP_ABI_VERSION stays 14. */
+size_t cvvdp_image_gradient_scratch_bytes(const cvvdp_handle* h);
+int cvvdp_image_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
+                         size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display

@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""Generate the fixtures of predict_with_gradient under tests/golden/grad/ by running the REAL reference on the CPU, with the import
+shims of oracle/ref_shims: `cvvdp(device='cpu').loss(test.requires_grad_(), ref).backward()` (pycvvdp/cvvdp_metric.py, the loss of
+examples/ex_image_reconstruction.py).  The inputs are those of tests/grad_reference.py (float32, fixed seeds).
+
+Written, one .npz per case of grad_reference.FIXTURES:
+  test, ref     float32 [1, 3, H, W]
+  display       the display's name
+  loss          float32, 10 - JOD
+  grad          float32 [1, 3, H, W], d loss / d test (the NEGATIVE of d JOD / d test)
+
+    python tools/make_goldens_grad.py
+"""
+import os
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+REFERENCE = os.environ.get("CVVDP_REFERENCE", os.path.join(ROOT, "..", "reference"))   # a checkout of the reference next to this one
+sys.path.insert(0, os.path.join(ROOT, "oracle", "ref_shims"))
+sys.path.insert(0, REFERENCE)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+import pycvvdp
+
+import grad_reference as gr
+
+
+def main():
+    os.makedirs(gr.GOLDEN, exist_ok=True)
+    for name in gr.FIXTURES:
+        test, ref, okw, display = gr.case(name)
+        m = pycvvdp.cvvdp(display_name=display, device=torch.device("cpu"), quiet=True)
+        t = test.clone().requires_grad_()
+        loss = m.loss(t, ref, dim_order="BCHW")
+        loss.backward()
+        g = t.grad.detach()
+        assert torch.isfinite(g).all() and float(g.abs().max()) > 0
+        np.savez_compressed(os.path.join(gr.GOLDEN, name + ".npz"), test=test.numpy(), ref=ref.numpy(), display=display,
+                            loss=np.float32(loss.detach().item()), grad=g.numpy().astype(np.float32))
+        print(f"{name}: loss {float(loss.detach()):.6f}  |grad| {float(g.norm()):.4e}")
+
+
+if __name__ == "__main__":
+    main()
