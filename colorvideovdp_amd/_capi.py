@@ -186,6 +186,9 @@ SYMBOLS = {
     "cvvdp_image_gradient_scratch_bytes": (C.c_size_t, [C.c_void_p]),
     "cvvdp_image_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_video_gradient_scratch_bytes": (C.c_size_t, [C.c_void_p]),
+    "cvvdp_video_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_preview_args_size": (C.c_int32, []),
     "cvvdp_pixel_preview": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(PreviewArgs), C.c_void_p, C.c_size_t, C.c_void_p]),

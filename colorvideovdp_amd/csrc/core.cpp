@@ -75,6 +75,10 @@ struct cvvdp_handle {
   hipEvent_t ev_reduce[2] = {nullptr, nullptr}, ev_band[2] = {nullptr, nullptr};
   bool band_pending[2] = {false, false};
   bool image_put = false, image_scored = false;   // image clips: cvvdp_put_image / cvvdp_process_image have run since cvvdp_configure (cvvdp_image_gradient)
+  // video clips (cvvdp_video_gradient): the last cvvdp_process_block scored the WHOLE clip from float32 frames handed in from frame 0
+  // on, and the padding map it was given (window position k < filter_len - 1 -> frame of the clip)
+  bool video_scored = false;
+  int16_t video_hist[CVVDP_MAX_FILTER_LEN] = {};
 };
 
 namespace {
@@ -619,6 +623,7 @@ int cvvdp_configure(cvvdp_handle* h, const cvvdp_clip* clip) {
   h->configured = true;
   h->last_items = 0; h->last_item0 = 0; h->last_q0 = 0;
   h->image_put = h->image_scored = false;
+  h->video_scored = false;
   return CVVDP_OK;
 }
 
@@ -1007,6 +1012,52 @@ GradLayout grad_layout(const cvvdp_handle* h) {
   g.total = off;
   return g;
 }
+// the band chain of a gradient plan (levels, baseband, pyramid adjoints) for NC channels over `items` items: forward planes from the
+// workspace, everything else at the given float offsets of the caller's scratch
+template <int NC>
+void fill_grad_chain(const cvvdp_handle* h, int items, float* sc, const size_t (&t)[3], const size_t* d, const size_t* ey, const float* coef,
+                     GradBandArgsT<NC>* band, GradBaseArgsT<NC>& base, GradAccumArgs* acc) {
+  const int L = h->L;
+  const float K[5] = {kGaussK0, 0.25f, 0.4f, 0.25f, kGaussK0};
+  for (int l = 0; l + 1 < L; ++l) {
+    const Level& lv = h->lv[l];
+    const Level& lc = h->lv[l + 1];
+    GradBandArgsT<NC>& a = band[l];
+    a.g = gbase(h, l, 0); a.gps = (int64_t)level_cap(h, l) * lv.P;
+    a.gc = gbase(h, l + 1, 0); a.gcps = (int64_t)h->items_cap_s * lc.P;
+    a.H = lv.H; a.W = lv.W; a.Hc = lc.H; a.Wc = lc.W; a.B = items; a.blur = lv.blur; a.level = l; a.L = L;
+    a.band_mul = l == 0 ? 1.0f : 2.0f;
+    std::memcpy(a.lut, h->c.csf_rows + (size_t)l * 4 * CVVDP_CSF_NODES, sizeof a.lut);
+    a.logL_first = h->p.csf_logL_first; a.logL_last = h->p.csf_logL_last; a.sens_mul = h->p.sens_mul;
+    for (int k = 0; k < NC; ++k) {
+      a.ch_gain[k] = h->p.ch_gain[k]; a.q[k] = h->p.mask_q[k]; a.eps_q[k] = std::pow(kEps, h->p.mask_q[k]);
+      for (int j = 0; j < NC; ++j) a.xw[k * NC + j] = h->p.xcm[k * 4 + j];
+    }
+    a.mask_c10 = h->p.mask_c10; a.mask_p = h->p.mask_p; a.eps_p = std::pow(kEps, h->p.mask_p); a.dmax = h->p.d_max10;
+    a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
+    for (int k = 0; k < 13; ++k) a.taps[k] = h->p.blur_taps[k];
+    a.coef = coef;
+    a.t0 = sc + t[0]; a.t1 = sc + t[1]; a.t2 = sc + t[2];
+    a.d = sc + d[l]; a.ey = sc + ey[l];
+  }
+  {
+    const Level& lv = h->lv[L - 1];
+    GradBaseArgsT<NC>& b = base;
+    b.g = gbase(h, L - 1, 0); b.gps = (int64_t)level_cap(h, L - 1) * lv.P;
+    b.H = lv.H; b.W = lv.W; b.B = items; b.level = L - 1; b.L = L;
+    std::memcpy(b.lut, h->c.csf_rows + (size_t)(L - 1) * 4 * CVVDP_CSF_NODES, sizeof b.lut);
+    b.logL_first = h->p.csf_logL_first; b.logL_last = h->p.csf_logL_last; b.sens_mul = h->p.sens_mul;
+    b.coef = coef; b.d = sc + d[L - 1];
+  }
+  for (int l = 0; l < L; ++l) {
+    GradAccumArgs& a = acc[l];
+    a.d = sc + d[l]; a.H = h->lv[l].H; a.W = h->lv[l].W; a.B = items;
+    if (l > 0) { a.d_f = sc + d[l - 1]; a.ey_f = sc + ey[l - 1]; a.Hf = h->lv[l - 1].H; a.Wf = h->lv[l - 1].W; }
+    if (l + 1 < L) { a.tot_c = sc + d[l + 1]; a.Hc = h->lv[l + 1].H; a.Wc = h->lv[l + 1].W; }
+    a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
+    for (int k = 0; k < 5; ++k) a.K[k] = K[k];
+  }
+}
 }  // namespace
 size_t cvvdp::grad_scratch(const cvvdp_handle* h) { return grad_clip_ok(h) ? grad_layout(h).total * sizeof(float) : 0; }
 int cvvdp::grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
@@ -1041,7 +1092,6 @@ int cvvdp::grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], 
     return fail(h, CVVDP_E_ARG, "image_gradient: scratch of %zu bytes, %zu needed", scratch_bytes, lay.total * sizeof(float));
   if (!h->ws || !h->image_scored) return fail(h, CVVDP_E_STATE, "image_gradient: valid after cvvdp_put_image and cvvdp_process_image");
   float* sc = static_cast<float*>(scratch);
-  const float K[5] = {kGaussK0, 0.25f, 0.4f, 0.25f, kGaussK0};
   plan = GradPlan{};
   plan.L = L;
   GradPoolArgs& po = plan.pool;
@@ -1049,44 +1099,7 @@ int cvvdp::grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], 
   for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
   for (int k = 0; k < 3; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
   po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp; po.image_int = h->p.image_int;
-  for (int l = 0; l + 1 < L; ++l) {
-    const Level& lv = h->lv[l];
-    const Level& lc = h->lv[l + 1];
-    GradBandArgs& a = plan.band[l];
-    a.g = gbase(h, l, 0); a.gps = (int64_t)level_cap(h, l) * lv.P;
-    a.gc = gbase(h, l + 1, 0); a.gcps = (int64_t)h->items_cap_s * lc.P;
-    a.H = lv.H; a.W = lv.W; a.Hc = lc.H; a.Wc = lc.W; a.B = B; a.blur = lv.blur; a.level = l; a.L = L;
-    a.band_mul = l == 0 ? 1.0f : 2.0f;
-    std::memcpy(a.lut, h->c.csf_rows + (size_t)l * 4 * CVVDP_CSF_NODES, sizeof a.lut);
-    a.logL_first = h->p.csf_logL_first; a.logL_last = h->p.csf_logL_last; a.sens_mul = h->p.sens_mul;
-    for (int k = 0; k < 3; ++k) {
-      a.ch_gain[k] = h->p.ch_gain[k]; a.q[k] = h->p.mask_q[k]; a.eps_q[k] = std::pow(kEps, h->p.mask_q[k]);
-      for (int j = 0; j < 3; ++j) a.xw[k * 3 + j] = h->p.xcm[k * 4 + j];
-    }
-    a.mask_c10 = h->p.mask_c10; a.mask_p = h->p.mask_p; a.eps_p = std::pow(kEps, h->p.mask_p); a.dmax = h->p.d_max10;
-    a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
-    for (int k = 0; k < 13; ++k) a.taps[k] = h->p.blur_taps[k];
-    a.coef = po.coef;
-    a.t0 = sc + lay.t[0]; a.t1 = sc + lay.t[1]; a.t2 = sc + lay.t[2];
-    a.d = sc + lay.d[l]; a.ey = sc + lay.ey[l];
-  }
-  {
-    const Level& lv = h->lv[L - 1];
-    GradBaseArgs& b = plan.base;
-    b.g = gbase(h, L - 1, 0); b.gps = (int64_t)level_cap(h, L - 1) * lv.P;
-    b.H = lv.H; b.W = lv.W; b.B = B; b.level = L - 1; b.L = L;
-    std::memcpy(b.lut, h->c.csf_rows + (size_t)(L - 1) * 4 * CVVDP_CSF_NODES, sizeof b.lut);
-    b.logL_first = h->p.csf_logL_first; b.logL_last = h->p.csf_logL_last; b.sens_mul = h->p.sens_mul;
-    b.coef = po.coef; b.d = sc + lay.d[L - 1];
-  }
-  for (int l = 0; l < L; ++l) {
-    GradAccumArgs& a = plan.acc[l];
-    a.d = sc + lay.d[l]; a.H = h->lv[l].H; a.W = h->lv[l].W; a.B = B;
-    if (l > 0) { a.d_f = sc + lay.d[l - 1]; a.ey_f = sc + lay.ey[l - 1]; a.Hf = h->lv[l - 1].H; a.Wf = h->lv[l - 1].W; }
-    if (l + 1 < L) { a.tot_c = sc + lay.d[l + 1]; a.Hc = h->lv[l + 1].H; a.Wc = h->lv[l + 1].W; }
-    a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
-    for (int k = 0; k < 5; ++k) a.K[k] = K[k];
-  }
+  fill_grad_chain<3>(h, B, sc, lay.t, lay.d, lay.ey, po.coef, plan.band, plan.base, plan.acc);
   GradDisplayArgs& d = plan.dsp;
   d.tot = sc + lay.d[0];
   d.test = static_cast<const float*>(test); d.tb = st[0]; d.tc = st[1]; d.th = st[3]; d.tw = st[4];
@@ -1096,6 +1109,100 @@ int cvvdp::grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], 
   return CVVDP_OK;
 }
 int cvvdp::grad_check_launch(cvvdp_handle* h) { return check_launch(h, "image_gradient"); }
+// cvvdp_video_gradient (grad_video.hip) up to the launches.  The caller's scratch, in floats, every part on a 256-byte granule, with
+// items = n_frames * batch: coef [items][4][L]; the FIR weight table [4][F][F]; three temporaries [4][items][P0]; per level d
+// [4][items][P_l] (level 0 ends up as G, what the FIR adjoint reads) and (all but the baseband) ey [items][P_l]
+namespace {
+struct GradVideoLayout { size_t coef, wt, t[3], d[CVVDP_MAX_LEVELS], ey[CVVDP_MAX_LEVELS], total; };
+// the configured clip is one the gradient exists for (what does not depend on the call order)
+bool grad_video_clip_ok(const cvvdp_handle* h) {
+  if (!h || !h->configured) return false;
+  const cvvdp_clip& c = h->c;
+  return c.is_video && c.channels == 3 && c.heatmap == CVVDP_HEATMAP_NONE && c.feature_size <= 0 && !c.defer_bands && c.block_frames >= c.n_frames &&
+         h->fuse_levels == 0 && !h->pipeline && (int64_t)c.n_frames * c.batch * 4 <= 65535;
+}
+GradVideoLayout grad_video_layout(const cvvdp_handle* h) {
+  GradVideoLayout g{};
+  const size_t F = (size_t)h->c.n_frames, items = F * (size_t)h->c.batch;
+  size_t off = 0;
+  g.coef = off; off += align_up(items * 4 * h->L);
+  g.wt = off; off += align_up(4 * F * F);
+  for (int k = 0; k < 3; ++k) { g.t[k] = off; off += align_up(4 * items * (size_t)h->lv[0].P); }
+  for (int l = 0; l < h->L; ++l) {
+    g.d[l] = off; off += align_up(4 * items * (size_t)h->lv[l].P);
+    g.ey[l] = off; if (l + 1 < h->L) off += align_up(items * (size_t)h->lv[l].P);
+  }
+  g.total = off;
+  return g;
+}
+}  // namespace
+size_t cvvdp::grad_video_scratch(const cvvdp_handle* h) { return grad_video_clip_ok(h) ? grad_video_layout(h).total * sizeof(float) : 0; }
+int cvvdp::grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes,
+                              void* scratch, size_t scratch_bytes, GradVideoPlan& plan) {
+  if (!h) return CVVDP_E_STATE;
+  if (!test || !st || !grad || !sg || !scratch) return fail(h, CVVDP_E_ARG, "video_gradient: null argument");
+  if (reinterpret_cast<uintptr_t>(test) % 4 || reinterpret_cast<uintptr_t>(grad) % 4 || reinterpret_cast<uintptr_t>(scratch) % 16)
+    return fail(h, CVVDP_E_ARG, "video_gradient: test and gradient must be 4-byte aligned, the scratch 16-byte aligned");
+  if (!h->configured) return fail(h, CVVDP_E_STATE, "video_gradient: configure first");
+  const cvvdp_clip& c = h->c;
+  if (!c.is_video) return fail(h, CVVDP_E_STATE, "video_gradient: configured for an image (cvvdp_image_gradient)");
+  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: 1-channel content is out of scope");
+  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: not with a heat map or features");
+  if (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG)
+    return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)");
+  if (c.defer_bands) return fail(h, CVVDP_E_STATE, "video_gradient: not for clips scored in pieces (defer_bands)");
+  if (c.block_frames < c.n_frames)
+    return fail(h, CVVDP_E_STATE, "video_gradient: the clip must be one temporal block (block_frames %d < n_frames %d)", c.block_frames, c.n_frames);
+  if (h->fuse_levels != 0 || h->pipeline)
+    return fail(h, CVVDP_E_STATE, "video_gradient: needs the unfused route (fuse_mode = 2), which keeps every pyramid level in the workspace");
+  const int B = c.batch, L = h->L, H = c.height, W = c.width, F = c.n_frames, fl = c.filter_len;
+  if ((int64_t)F * B * 4 > 65535)      // (4 planes per item in a grid's y)
+    return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: %d frames x %d batch items are too many (4 planes per item, 65535 at most)", F, B);
+  // the gradient's extent: the last element written is sum (size - 1) * stride over B, C, F, H, W
+  {
+    const int64_t dims[5] = {B, 3, F, H, W};
+    int64_t last = 0, term = 0;
+    bool bad = false;
+    for (int k = 0; k < 5 && !bad; ++k)
+      bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
+    if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
+      return fail(h, CVVDP_E_ARG, "video_gradient: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d x %d samples at these strides", grad_bytes,
+                  B, F, H, W);
+  }
+  const GradVideoLayout lay = grad_video_layout(h);
+  if (scratch_bytes < lay.total * sizeof(float))
+    return fail(h, CVVDP_E_ARG, "video_gradient: scratch of %zu bytes, %zu needed", scratch_bytes, lay.total * sizeof(float));
+  if (!h->ws || !h->video_scored)
+    return fail(h, CVVDP_E_STATE, "video_gradient: valid after the cvvdp_process_block that scored all %d frames from float32 frames", F);
+  float* sc = static_cast<float*>(scratch);
+  plan = GradVideoPlan{};
+  plan.L = L; plan.items = F * B;
+  GradVideoPoolArgs& po = plan.pool;
+  po.q = h->ws + h->q_off; po.coef = sc + lay.coef; po.B = B; po.F = F; po.L = L;
+  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
+  for (int k = 0; k < 4; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
+  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.beta_t = h->p.beta_t; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp;
+  fill_grad_chain<4>(h, F * B, sc, lay.t, lay.d, lay.ey, po.coef, plan.band, plan.base, plan.acc);
+  // the taps as the forward applies them: tflip[c][k] multiplies window position k (F.flip(0), cvvdp_metric.py:556)
+  bool replicate = true;
+  for (int k = 0; k + 1 < fl; ++k) replicate = replicate && h->video_hist[k] == 0;
+  GradFirWeightArgs& fw = plan.fw;
+  fw.wt = sc + lay.wt; fw.F = F; fw.fl = fl;
+  for (int ch = 0; ch < 4; ++ch)
+    for (int k = 0; k < fl; ++k) fw.tflip[ch * CVVDP_MAX_FILTER_LEN + k] = c.taps[ch * CVVDP_MAX_FILTER_LEN + (fl - 1 - k)];
+  for (int k = 0; k + 1 < fl; ++k) fw.src[k] = h->video_hist[k];
+  GradFirAdjArgs& a = plan.fir;
+  a.G = sc + lay.d[0]; a.wt = fw.wt;
+  a.test = static_cast<const float*>(test); a.tb = st[0]; a.tc = st[1]; a.tf = st[2]; a.th = st[3]; a.tw = st[4];
+  a.grad = grad; a.gb = sg[0]; a.gc = sg[1]; a.gf = sg[2]; a.gh = sg[3]; a.gw = sg[4];
+  a.H = H; a.W = W; a.B = B; a.F = F; a.fl = fl;
+  a.reg_wl = (!replicate || fl > CVVDP_GRAD_FIR_WL) ? 0 : (fl <= 9 ? 9 : (fl <= 17 ? 17 : CVVDP_GRAD_FIR_WL));
+  for (int ch = 0; ch < 4; ++ch)
+    for (int k = 0; k < fl && k < CVVDP_GRAD_FIR_WL; ++k) a.tflip[ch * CVVDP_GRAD_FIR_WL + k] = fw.tflip[ch * CVVDP_MAX_FILTER_LEN + k];
+  fill_display(h, a.dm);
+  return CVVDP_OK;
+}
+int cvvdp::grad_video_check_launch(cvvdp_handle* h) { return check_launch(h, "video_gradient"); }
 // cvvdp_pixel_preview (preview.hip) up to the launch: the source checks of cvvdp_pixel_sse on one side, then the target, the format and
 // the canvas.  Nothing is launched unless the last pixel of the last frame lies inside dst_bytes.
 int cvvdp::preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref,
@@ -1335,8 +1442,17 @@ static int process_block_impl(cvvdp_handle* h, const void* t, const void* r, int
     launch_fir(f, h->ws + h->hist_shadow_off, s);
   }
   if (int e = check_launch(h, "temporal fir")) return e;
+  h->video_scored = false;
   if (c.defer_bands) { h->filtered_frames = n_frames; h->filtered_q0 = q_frame_offset; return CVVDP_OK; }   // scored in pieces: cvvdp_score_frames
-  return run_pyramid_and_bands(h, n_frames, q_frame_offset, s);
+  const int rc = run_pyramid_and_bands(h, n_frames, q_frame_offset, s);
+  // what cvvdp_video_gradient needs of this call: the whole clip in one block, raw float32 frames from frame 0, padding from the clip itself
+  bool whole = rc == CVVDP_OK && dtype == CVVDP_F32 && !yuv && raw_first == 0 && q_frame_offset == 0 && n_frames == c.n_frames && c.first_frame == 0;
+  for (int k = 0; k < fl_clip - 1 && whole; ++k) {
+    whole = hist_src[k] >= 0 && hist_src[k] < n_frames;
+    h->video_hist[k] = (int16_t)hist_src[k];
+  }
+  h->video_scored = whole;
+  return rc;
 }
 
 int cvvdp_process_block_filtered(cvvdp_handle* h, const void* t, const void* r, const int64_t st[5], const int64_t sr[5],

@@ -33,12 +33,14 @@ __global__ __launch_bounds__(64) void k_grad_pool(const GradPoolArgs a) {
   if (b < a.B) g_pool_coef(a, a.q + (int64_t)b * 3 * a.L, a.coef + (int64_t)b * 3 * a.L);
 }
 
-__global__ __launch_bounds__(GT) void k_grad_min(const GradBandArgs a) {
+// (the kernels of the band chain: NC = 3 for images, 4 for video -- grad_video.hip runs the same chain over frames x batch items)
+template <int NC>
+__global__ __launch_bounds__(GT) void k_grad_min(const GradBandArgsT<NC> a) {
   GRAD_PIXEL(a.H, a.W);
   const int item = blockIdx.y;
-  float m[3];
+  float m[NC];
   g_band_min(a, item, y, x, m);
-  for (int c = 0; c < 3; ++c) a.t0[((int64_t)c * a.B + item) * P + i] = m[c];
+  for (int c = 0; c < NC; ++c) a.t0[((int64_t)c * a.B + item) * P + i] = m[c];
 }
 
 // one axis of the blur (or of its adjoint) over n_planes planes of H x W
@@ -52,59 +54,63 @@ __global__ __launch_bounds__(GT) void k_grad_blur(const GradBlurArgs a) {
   a.out[(int64_t)blockIdx.y * P + i] = a.adjoint ? g_blur_adj(line, stride, n, k, a.w) : g_blur_fwd(line, stride, n, k, a.w);
 }
 
-__global__ __launch_bounds__(GT) void k_grad_point(const GradBandArgs a) {
+template <int NC>
+__global__ __launch_bounds__(GT) void k_grad_point(const GradBandArgsT<NC> a) {
   GRAD_PIXEL(a.H, a.W);
   const int item = blockIdx.y;
-  float v[3], G[3], dir[3];
-  for (int c = 0; c < 3; ++c) v[c] = a.t0[((int64_t)c * a.B + item) * P + i];
+  float v[NC], G[NC], dir[NC];
+  for (int c = 0; c < NC; ++c) v[c] = a.t0[((int64_t)c * a.B + item) * P + i];
   g_band_point(a, item, y, x, v, G, dir);
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < NC; ++c) {
     a.t1[((int64_t)c * a.B + item) * P + i] = G[c];
     a.t2[((int64_t)c * a.B + item) * P + i] = dir[c];
   }
 }
 
-__global__ __launch_bounds__(GT) void k_grad_contrast(const GradBandArgs a) {
+template <int NC>
+__global__ __launch_bounds__(GT) void k_grad_contrast(const GradBandArgsT<NC> a) {
   GRAD_PIXEL(a.H, a.W);
   const int item = blockIdx.y;
-  float gm[3], dir[3], d[3], ey;
-  for (int c = 0; c < 3; ++c) {
+  float gm[NC], dir[NC], d[NC], ey;
+  for (int c = 0; c < NC; ++c) {
     gm[c] = a.t1[((int64_t)c * a.B + item) * P + i];
     dir[c] = a.t2[((int64_t)c * a.B + item) * P + i];
   }
   g_band_contrast(a, item, y, x, gm, dir, d, ey);
-  for (int c = 0; c < 3; ++c) a.d[((int64_t)c * a.B + item) * P + i] = d[c];
+  for (int c = 0; c < NC; ++c) a.d[((int64_t)c * a.B + item) * P + i] = d[c];
   a.ey[(int64_t)item * P + i] = ey;
 }
 
 // One block per item (the band is at most a few hundred samples): the mean backgrounds, then per sample the direct part and its share
 // of dJOD/dLt, then the mean's own gradient to every test Y sample at or above the clamp
-__global__ __launch_bounds__(256) void k_grad_base(const GradBaseArgs a) {
+template <int NC>
+__global__ __launch_bounds__(256) void k_grad_base(const GradBaseArgsT<NC> a) {
   __shared__ float s_tmp[4];
   const int item = blockIdx.x, t = threadIdx.x;
   const int P = a.H * a.W;
   const float* g = a.g + (int64_t)item * P;
   float Lb[2];
   base_bkg_mean<2>(g, a.gps, P, s_tmp, Lb);
-  float S[3];
+  float S[NC];
   g_base_sens(a, Lb[1], S);
   float gL = 0.0f;
   for (int i = t; i < P; i += 256) {
-    float d[3];
+    float d[NC];
     gL += g_base_pixel(a, item, i, Lb[0], Lb[1], S, d);
-    for (int c = 0; c < 3; ++c) a.d[((int64_t)c * a.B + item) * P + i] = d[c];
+    for (int c = 0; c < NC; ++c) a.d[((int64_t)c * a.B + item) * P + i] = d[c];
   }
   gL = block_sum(gL, s_tmp) / (float)P;
   for (int i = t; i < P; i += 256)          // (each thread revisits the samples it wrote itself)
     if (g[i] >= 0.01f) a.d[(int64_t)item * P + i] += gL;
 }
 
+template <int NC>
 __global__ __launch_bounds__(GT) void k_grad_accum(const GradAccumArgs a) {
   GRAD_PIXEL(a.H, a.W);
   const int item = blockIdx.y;
   GradAccum s{a.H, a.W, a.Hf, a.Wf, a.Hc, a.Wc};
   const int64_t Pf = (int64_t)a.Hf * a.Wf, Pc = (int64_t)a.Hc * a.Wc;
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < NC; ++c) {
     float* own = a.d + ((int64_t)c * a.B + item) * P + i;
     const float* ex_f = !a.d_f ? nullptr : (c == 0 ? a.ey_f + (int64_t)item * Pf : a.d_f + ((int64_t)c * a.B + item) * Pf);
     const float* tot_c = a.tot_c ? a.tot_c + ((int64_t)c * a.B + item) * Pc : nullptr;
@@ -133,29 +139,39 @@ void blur_pass(const float* in, float* out, int H, int W, int planes, bool verti
   hipLaunchKernelGGL(k_grad_blur, pixel_grid(H, W, planes), dim3(GT), 0, s, b);
 }
 
+// levels finest first, the baseband, then the totals coarsest first: B items of NC channels (NC * B planes fit a grid's y: core.cpp checks)
+template <int NC>
+void launch_chain(int L, int B, const GradBandArgsT<NC>* band, const GradBaseArgsT<NC>& base, const GradAccumArgs* acc, hipStream_t s) {
+  for (int l = 0; l + 1 < L; ++l) {
+    const GradBandArgsT<NC>& a = band[l];
+    const dim3 grid = pixel_grid(a.H, a.W, B);
+    hipLaunchKernelGGL(k_grad_min<NC>, grid, dim3(GT), 0, s, a);
+    if (a.blur) {
+      blur_pass(a.t0, a.t1, a.H, a.W, NC * B, true, false, a.taps, s);
+      blur_pass(a.t1, a.t0, a.H, a.W, NC * B, false, false, a.taps, s);
+    }
+    hipLaunchKernelGGL(k_grad_point<NC>, grid, dim3(GT), 0, s, a);
+    if (a.blur) {
+      blur_pass(a.t1, a.t0, a.H, a.W, NC * B, false, true, a.taps, s);
+      blur_pass(a.t0, a.t1, a.H, a.W, NC * B, true, true, a.taps, s);
+    }
+    hipLaunchKernelGGL(k_grad_contrast<NC>, grid, dim3(GT), 0, s, a);
+  }
+  hipLaunchKernelGGL(k_grad_base<NC>, dim3(B), dim3(256), 0, s, base);
+  for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum<NC>, pixel_grid(acc[l].H, acc[l].W, B), dim3(GT), 0, s, acc[l]);
+}
+
 }  // namespace
 
 void launch_image_gradient(const GradPlan& p, hipStream_t s) {
   const int B = p.pool.B;
   hipLaunchKernelGGL(k_grad_pool, dim3((B + 63) / 64), dim3(64), 0, s, p.pool);
-  for (int l = 0; l + 1 < p.L; ++l) {
-    const GradBandArgs& a = p.band[l];
-    const dim3 grid = pixel_grid(a.H, a.W, B);
-    hipLaunchKernelGGL(k_grad_min, grid, dim3(GT), 0, s, a);
-    if (a.blur) {
-      blur_pass(a.t0, a.t1, a.H, a.W, 3 * B, true, false, a.taps, s);
-      blur_pass(a.t1, a.t0, a.H, a.W, 3 * B, false, false, a.taps, s);
-    }
-    hipLaunchKernelGGL(k_grad_point, grid, dim3(GT), 0, s, a);
-    if (a.blur) {
-      blur_pass(a.t1, a.t0, a.H, a.W, 3 * B, false, true, a.taps, s);
-      blur_pass(a.t0, a.t1, a.H, a.W, 3 * B, true, true, a.taps, s);
-    }
-    hipLaunchKernelGGL(k_grad_contrast, grid, dim3(GT), 0, s, a);
-  }
-  hipLaunchKernelGGL(k_grad_base, dim3(B), dim3(256), 0, s, p.base);
-  for (int l = p.L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum, pixel_grid(p.acc[l].H, p.acc[l].W, B), dim3(GT), 0, s, p.acc[l]);
+  launch_chain<3>(p.L, B, p.band, p.base, p.acc, s);
   hipLaunchKernelGGL(k_grad_display, pixel_grid(p.dsp.H, p.dsp.W, B), dim3(GT), 0, s, p.dsp);
+}
+
+void launch_grad_chain4(int L, int items, const GradBandArgsT<4>* band, const GradBaseArgsT<4>& base, const GradAccumArgs* acc, hipStream_t s) {
+  launch_chain<4>(L, items, band, base, acc, s);
 }
 
 }  // namespace cvvdp

@@ -1,7 +1,8 @@
 // Per-element maths of the backward pass of the image metric (grad.hip, cvvdp_image_gradient): every function computes ONE output
 // element from the elements it depends on (a gather), so the kernels around them are index arithmetic only.  The functions compile for
 // the host as well: tests/native/grad_host_check.cpp walks the same code over small images on the CPU.
-// Forward graph and the reference lines it follows: DESIGN.md 7f.
+// Forward graph and the reference lines it follows: DESIGN.md 7f.  The band functions are templates on the channel count: 3 for
+// images, 4 for video (grad_video_dev.h), where the items are frames x batch.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -122,19 +123,24 @@ GRAD_HD float g_blur_adj(const float* in, int64_t stride, int n, int i, const fl
 }
 
 // ---------------------------------------------------------------- one Laplacian level: forward values of a pixel
-struct GradPixel {
-  float Tp[3], Rp[3];      // T' = T * S * gain, R' likewise (cvvdp_metric.py:835-836)
-  float layer[3];          // test Laplacian sample g_l - expand(g_l+1)
-  float S[3];              // sensitivity * channel gain (from the REFERENCE's background: a constant of the gradient)
+template <int NC>
+struct GradPixelT {
+  float Tp[NC], Rp[NC];      // T' = T * S * gain, R' likewise (cvvdp_metric.py:835-836)
+  float layer[NC];         // test Laplacian sample g_l - expand(g_l+1)
+  float S[NC];             // sensitivity * channel gain (from the REFERENCE's background: a constant of the gradient)
   float Lt, exY;           // test background max(exY, 0.01) and the expanded test Y it comes from
 };
+using GradPixel = GradPixelT<3>;
 
-GRAD_HD void g_band_pixel(const GradBandArgs& a, int item, int y, int x, GradPixel& o) {
+// NC = 4 (video): channel 3 is the transient one -- planes 6 / 7, CSF row 3, its own gain, mask exponent and cross-channel weights; its
+// contrast is divided by the sustained-Y background like the others
+template <int NC>
+GRAD_HD void g_band_pixel(const GradBandArgsT<NC>& a, int item, int y, int x, GradPixelT<NC>& o) {
   const int64_t P = (int64_t)a.H * a.W, Pc = (int64_t)a.Hc * a.Wc;
   const float* g = a.g + (int64_t)item * P + (int64_t)y * a.W + x;
   const float* gc = a.gc + (int64_t)item * Pc;
-  float ext[3], exr[3];
-  for (int c = 0; c < 3; ++c) {
+  float ext[NC], exr[NC];
+  for (int c = 0; c < NC; ++c) {
     ext[c] = g_expand_at(gc + (2 * c) * a.gcps, a.Hc, a.Wc, y, x, a.kx);
     exr[c] = g_expand_at(gc + (2 * c + 1) * a.gcps, a.Hc, a.Wc, y, x, a.kx);
   }
@@ -145,7 +151,7 @@ GRAD_HD void g_band_pixel(const GradBandArgs& a, int item, int y, int x, GradPix
   const int i0 = (int)ind, i1 = g_min(i0 + 1, CVVDP_CSF_NODES - 1);
   const float fr = ind - (float)i0;
   o.Lt = Lt; o.exY = ext[0];
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < NC; ++c) {
     const float l0 = a.lut[c * CVVDP_CSF_NODES + i0], l1 = a.lut[c * CVVDP_CSF_NODES + i1];
     const float S = g_exp2((l0 + (l1 - l0) * fr) * kLog2_10) * a.sens_mul * a.ch_gain[c];       // csf.py:49, cvvdp_metric.py:709, :836
     const float lt = g[(2 * c) * a.gps] - ext[c], lr = g[(2 * c + 1) * a.gps] - exr[c];
@@ -156,51 +162,55 @@ GRAD_HD void g_band_pixel(const GradBandArgs& a, int item, int y, int x, GradPix
 }
 
 // pass 1: m = min(|T'|, |R'|) (cvvdp_metric.py:845)
-GRAD_HD void g_band_min(const GradBandArgs& a, int item, int y, int x, float (&m)[3]) {
-  GradPixel px;
+template <int NC>
+GRAD_HD void g_band_min(const GradBandArgsT<NC>& a, int item, int y, int x, float (&m)[NC]) {
+  GradPixelT<NC> px;
   g_band_pixel(a, item, y, x, px);
-  for (int c = 0; c < 3; ++c) m[c] = fminf(fabsf(px.Tp[c]), fabsf(px.Rp[c]));
+  for (int c = 0; c < NC; ++c) m[c] = fminf(fabsf(px.Tp[c]), fabsf(px.Rp[c]));
 }
 
 // pass 3: from the (blurred) mask v = Mmm / 10^mask_c of the pixel, with gD = dJOD/dD:
 //   G[k]   = dJOD/dv[k]: the masking term gM = -gDu Du / (1 + M) through the transposed cross-channel weights and safe_pow'
 //   dir[c] = the part of dJOD/dT'[c] that comes straight through |T' - R'|
-GRAD_HD void g_band_point(const GradBandArgs& a, int item, int y, int x, const float (&v)[3], float (&G)[3], float (&dir)[3]) {
-  GradPixel px;
+template <int NC>
+GRAD_HD void g_band_point(const GradBandArgsT<NC>& a, int item, int y, int x, const float (&v)[NC], float (&G)[NC], float (&dir)[NC]) {
+  GradPixelT<NC> px;
   g_band_pixel(a, item, y, x, px);
-  float C[3], Mm[3];
-  for (int k = 0; k < 3; ++k) {
+  float C[NC], Mm[NC];
+  for (int k = 0; k < NC; ++k) {
     Mm[k] = v[k] * a.mask_c10;
     C[k] = g_pow(fabsf(Mm[k]) + kEps, a.q[k]) - a.eps_q[k];                           // safe_pow(|Mmm|, q), :753-757
   }
-  float gM[3];
-  for (int c = 0; c < 3; ++c) {
+  float gM[NC];
+  for (int c = 0; c < NC; ++c) {
     float M = 0.0f;
-    for (int k = 0; k < 3; ++k) M += C[k] * a.xw[k * 3 + c];                          // :758-760
+    for (int k = 0; k < NC; ++k) M += C[k] * a.xw[k * NC + c];                          // :758-760
     const float diff = px.Tp[c] - px.Rp[c], d = fabsf(diff);
     const float inv1M = 1.0f / (1.0f + M);
     const float Du = (g_pow(d + kEps, a.mask_p) - a.eps_p) * inv1M;                   // :856
     const float sum = a.dmax + Du;
     const float D = a.dmax * Du / sum;                                                // soft clamp, :949-950
-    const float gD = a.coef[((int64_t)item * 3 + c) * a.L + a.level] * (D + kEps);    // lp_norm, beta = 2: coef holds dJOD/dQ / (N (Q + sqrt(eps)))
+    const float gD = a.coef[((int64_t)item * NC + c) * a.L + a.level] * (D + kEps);   // lp_norm, beta = 2: coef holds dJOD/dQ / (N (Q + sqrt(eps)))
     const float gDu = gD * (a.dmax / sum) * (a.dmax / sum);
     dir[c] = gDu * inv1M * a.mask_p * g_pow(d + kEps, a.mask_p - 1.0f) * g_sign(diff);
     gM[c] = -gDu * Du * inv1M;
   }
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < NC; ++k) {
     float gC = 0.0f;
-    for (int c = 0; c < 3; ++c) gC += gM[c] * a.xw[k * 3 + c];
+    for (int c = 0; c < NC; ++c) gC += gM[c] * a.xw[k * NC + c];
     G[k] = gC * a.q[k] * g_pow(fabsf(Mm[k]) + kEps, a.q[k] - 1.0f) * g_sign(Mm[k]) * a.mask_c10;
   }
 }
 
 // pass 5: gm = dJOD/dm (the blur's adjoint of G), dir from pass 3 -> d[c] = dJOD/d(layer_c) (= the direct part of dJOD/dg_l) and
 // ey = dJOD/d(expanded test Y); the expanded chroma planes receive -d[c]
-GRAD_HD void g_band_contrast(const GradBandArgs& a, int item, int y, int x, const float (&gm)[3], const float (&dir)[3], float (&d)[3], float& ey) {
-  GradPixel px;
+template <int NC>
+GRAD_HD void g_band_contrast(const GradBandArgsT<NC>& a, int item, int y, int x, const float (&gm)[NC], const float (&dir)[NC], float (&d)[NC],
+                             float& ey) {
+  GradPixelT<NC> px;
   g_band_pixel(a, item, y, x, px);
   float gL = 0.0f;
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < NC; ++c) {
     const float at = fabsf(px.Tp[c]), ar = fabsf(px.Rp[c]);
     const float w = at < ar ? 1.0f : (at == ar ? 0.5f : 0.0f);                        // torch.min(a, b): ties share the gradient
     const float gTp = dir[c] + gm[c] * w * g_sign(px.Tp[c]);
@@ -214,24 +224,26 @@ GRAD_HD void g_band_contrast(const GradBandArgs& a, int item, int y, int x, cons
 
 // ---------------------------------------------------------------- baseband (lpyr_dec.py:378-384, cvvdp_metric.py:711-712)
 // sensitivities at the reference's mean background Lr (k_baseband's expressions)
-GRAD_HD void g_base_sens(const GradBaseArgs& a, float Lr, float (&S)[3]) {
+template <int NC>
+GRAD_HD void g_base_sens(const GradBaseArgsT<NC>& a, float Lr, float (&S)[NC]) {
   float ind = (log10f(Lr) - a.logL_first) / (a.logL_last - a.logL_first) * (float)(CVVDP_CSF_NODES - 1);
   ind = fminf(fmaxf(ind, 0.0f), (float)(CVVDP_CSF_NODES - 1));
   const int i0 = (int)ind, i1 = g_min(i0 + 1, CVVDP_CSF_NODES - 1);
   const float fr = ind - (float)i0;
-  for (int c = 0; c < 3; ++c) S[c] = exp10f(a.lut[c * CVVDP_CSF_NODES + i0] * (1.0f - fr) + a.lut[c * CVVDP_CSF_NODES + i1] * fr) * a.sens_mul;
+  for (int c = 0; c < NC; ++c) S[c] = exp10f(a.lut[c * CVVDP_CSF_NODES + i0] * (1.0f - fr) + a.lut[c * CVVDP_CSF_NODES + i1] * fr) * a.sens_mul;
 }
 // sample i of the item: d[c] = dJOD/dg[c] without the part through the mean background; returns this sample's share of dJOD/dLt
-GRAD_HD float g_base_pixel(const GradBaseArgs& a, int item, int i, float Lt, float Lr, const float (&S)[3], float (&d)[3]) {
+template <int NC>
+GRAD_HD float g_base_pixel(const GradBaseArgsT<NC>& a, int item, int i, float Lt, float Lr, const float (&S)[NC], float (&d)[NC]) {
   const int64_t P = (int64_t)a.H * a.W;
   const float* g = a.g + (int64_t)item * P + i;
   float gL = 0.0f;
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < NC; ++c) {
     const float gt = g[(2 * c) * a.gps], gr = g[(2 * c + 1) * a.gps];
     const float rt = gt / Lt;
     const float diff = fminf(rt, 1000.0f) - fminf(gr / Lr, 1000.0f);
     const float D = fabsf(diff) * S[c];
-    const float gD = a.coef[((int64_t)item * 3 + c) * a.L + a.level] * (D + kEps);
+    const float gD = a.coef[((int64_t)item * NC + c) * a.L + a.level] * (D + kEps);
     const float gx = rt <= 1000.0f ? gD * S[c] * g_sign(diff) : 0.0f;
     d[c] = gx / Lt;
     gL -= gx * gt / (Lt * Lt);

@@ -609,33 +609,37 @@ struct GradPoolArgs {        // dJOD/dQ_per_ch, folded with the derivative of th
   float ch_w[3], bb_w[3];
   float beta_sch, beta_tch, jod_a, jod_exp, image_int;
 };
-struct GradBandArgs {        // one Laplacian level
+template <int NC>
+struct GradBandArgsT {       // one Laplacian level of NC channels (3: image; 4: video, channel 3 = the transient one); B counts ITEMS
   const float* g;  int64_t gps;     // level l: plane p of item i at g + p * gps + i * H * W
   const float* gc; int64_t gcps;    // level l + 1
   int32_t H, W, Hc, Wc, B, blur;
   int32_t level, L;
   float band_mul;
-  float lut[3 * CVVDP_CSF_NODES];
+  float lut[NC * CVVDP_CSF_NODES];
   float logL_first, logL_last, sens_mul;
-  float ch_gain[3], q[3], eps_q[3];
+  float ch_gain[NC], q[NC], eps_q[NC];
   float mask_c10, mask_p, eps_p, dmax;
-  float xw[9];               // [k][c]: weight of channel k's mask in channel c
+  float xw[NC * NC];         // [k][c]: weight of channel k's mask in channel c
   float kx[3];               // expand taps (BandArgs.kx)
   float taps[13];
-  const float* coef;         // [B][3][L]
-  float *t0, *t1, *t2;       // temporaries, [3][B][H * W] each
-  float* d;                  // out: dJOD/d(layer) [3][B][H * W]
+  const float* coef;         // [B][NC][L]
+  float *t0, *t1, *t2;       // temporaries, [NC][B][H * W] each
+  float* d;                  // out: dJOD/d(layer) [NC][B][H * W]
   float* ey;                 // out: dJOD/d(expanded test Y) [B][H * W]
 };
-struct GradBaseArgs {        // the baseband
+using GradBandArgs = GradBandArgsT<3>;
+template <int NC>
+struct GradBaseArgsT {       // the baseband
   const float* g; int64_t gps;
   int32_t H, W, B, level, L;
-  float lut[3 * CVVDP_CSF_NODES];
+  float lut[NC * CVVDP_CSF_NODES];
   float logL_first, logL_last, sens_mul;
   const float* coef;
-  float* d;                  // out: dJOD/dg [3][B][H * W]
+  float* d;                  // out: dJOD/dg [NC][B][H * W]
 };
-struct GradAccumArgs {       // level l: d (direct) -> total, in place; coarsest level first
+using GradBaseArgs = GradBaseArgsT<3>;
+struct GradAccumArgs {       // level l: d (direct) -> total, in place; coarsest level first (the [3] below: [4] for video)
   float* d;                  // [3][B][H * W]
   const float* d_f;          // finer level's d [3][B][Hf * Wf] (still its direct part) and ey [B][Hf * Wf], or null at level 0
   const float* ey_f;
@@ -658,12 +662,58 @@ struct GradPlan {            // everything cvvdp_image_gradient launches, filled
   GradAccumArgs acc[CVVDP_MAX_LEVELS];
   GradDisplayArgs dsp;
 };
-static_assert(sizeof(GradBandArgs) <= 4096 && sizeof(GradDisplayArgs) <= 4096, "kernel arguments of the gradient kernels");
+static_assert(sizeof(GradBandArgsT<4>) <= 4096 && sizeof(GradDisplayArgs) <= 4096, "kernel arguments of the gradient kernels");
 // core.cpp: scratch size of the configured clip (0: no gradient for it), argument / state checks and the plan; the error of a launch
 size_t grad_scratch(const cvvdp_handle* h);
 int grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
                  size_t scratch_bytes, GradPlan& plan);
 int grad_check_launch(cvvdp_handle* h);
 void launch_image_gradient(const GradPlan& p, hipStream_t s);
+
+// ---------------------------------------------------------------- gradient of the video JOD (grad_video.hip, grad_video_dev.h)
+// d JOD[b] / d test[b] of a clip scored as ONE temporal block on the unfused route: the band chain above with four channels over
+// items = frames x batch (item = frame * B + b, the forward's order), then the adjoint of the temporal FIR fused with the display model's.
+struct GradVideoPoolArgs {   // dJOD/dQ_per_ch with the pooling over frames (grad_video_dev.h g_vpool_*)
+  const float* q;           // Q_per_ch [B][4][F][L]
+  float* coef;              // [F * B][4][L]: item-major, what the band chain indexes
+  int32_t B, F, L;
+  int32_t n_px[CVVDP_MAX_LEVELS];
+  float ch_w[4], bb_w[4];
+  float beta_sch, beta_tch, beta_t, jod_a, jod_exp;
+};
+struct GradFirWeightArgs {   // the gather variant's table: wt[c][j][f] = weight of G_c[f] in the DKL plane of test frame j
+  float* wt;                // [4][F][F]
+  int32_t F, fl;
+  float tflip[4 * CVVDP_MAX_FILTER_LEN];     // [c][k]: multiplies window position k (FirArgs.taps)
+  int16_t src[CVVDP_MAX_FILTER_LEN];         // window position k < fl - 1 -> test frame (the forward's hist_src)
+};
+constexpr int CVVDP_GRAD_FIR_WL = 33;        // longest filter of the register variant of the FIR adjoint
+struct GradFirAdjArgs {      // G = dJOD/d(level-0 planes) -> dJOD/dV through FIR^T, M^T and the EOTF's slope, written through the caller's strides
+  const float* G;           // [4][F * B][H * W]
+  const float* wt;          // gather variant only
+  const float* test; int64_t tb, tc, tf, th, tw;
+  float* grad; int64_t gb, gc, gf, gh, gw;
+  int32_t H, W, B, F, fl;
+  int32_t reg_wl;           // 0: gather variant; else the register variant's window (9, 17 or 33 >= fl; replicate padding only)
+  float tflip[4 * CVVDP_GRAD_FIR_WL];        // register variant: [c][k], zero from fl on
+  DisplayArgs dm;
+};
+struct GradVideoPlan {       // everything cvvdp_video_gradient launches, filled by core.cpp
+  int32_t L, items;
+  GradVideoPoolArgs pool;
+  GradBandArgsT<4> band[CVVDP_MAX_LEVELS];
+  GradBaseArgsT<4> base;
+  GradAccumArgs acc[CVVDP_MAX_LEVELS];
+  GradFirWeightArgs fw;
+  GradFirAdjArgs fir;
+};
+static_assert(sizeof(GradFirAdjArgs) <= 4096 && sizeof(GradFirWeightArgs) <= 4096, "kernel arguments of the video gradient kernels");
+size_t grad_video_scratch(const cvvdp_handle* h);
+int grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
+                       size_t scratch_bytes, GradVideoPlan& plan);
+int grad_video_check_launch(cvvdp_handle* h);
+// grad.hip: the band chain (levels, baseband, pyramid adjoints) for 4 channels; grad_video.hip: pooling and the FIR / display adjoint
+void launch_grad_chain4(int L, int items, const GradBandArgsT<4>* band, const GradBaseArgsT<4>& base, const GradAccumArgs* acc, hipStream_t s);
+void launch_video_gradient(const GradVideoPlan& p, hipStream_t s);
 
 }  // namespace cvvdp

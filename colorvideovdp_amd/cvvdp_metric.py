@@ -268,8 +268,8 @@ class _JodLoss(torch.autograd.Function):
     """10 - JOD with the gradient of cvvdp.predict_with_gradient (cvvdp.differentiable_loss)."""
 
     @staticmethod
-    def forward(ctx, test, reference, metric, dim_order):
-        jod, grad = metric.predict_with_gradient(test, reference, dim_order)
+    def forward(ctx, test, reference, metric, dim_order, frames_per_second):
+        jod, grad = metric.predict_with_gradient(test, reference, dim_order, frames_per_second)
         ctx.save_for_backward(grad)
         ctx.batch_shape = [n if ch == "B" else 1 for ch, n in zip(dim_order.upper(), grad.shape)]
         return 10.0 - jod
@@ -278,7 +278,7 @@ class _JodLoss(torch.autograd.Function):
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
         up = upstream if upstream.dim() == 0 else upstream.reshape(ctx.batch_shape)      # one factor per batch item
-        return -grad * up, None, None, None
+        return -grad * up, None, None, None, None
 
 
 class cvvdp(vq_metric):
@@ -546,11 +546,11 @@ class cvvdp(vq_metric):
         for a in (test_cont, reference_cont):
             if torch.is_tensor(a) and a.requires_grad:
                 raise vq_exception("colorvideovdp_amd is inference-only: loss() does not propagate gradients "
-                                   "(differentiable_loss() does, for images)")
+                                   "(differentiable_loss() does, for images and for clips scored as one block)")
         Q_jod, _ = self.predict(test_cont, reference_cont, dim_order=dim_order, frames_per_second=frames_per_second)
         return 10.0 - Q_jod
 
-    def _gradient_inputs(self, test, reference, dim_order):
+    def _gradient_inputs(self, test, reference, dim_order, frames_per_second=0):
         """What predict_with_gradient refuses, checked before anything touches the device; returns the BCFHW views."""
         if not torch.is_tensor(test) or not torch.is_tensor(reference):
             raise vq_exception("predict_with_gradient: test and reference must be torch tensors")
@@ -564,8 +564,17 @@ class cvvdp(vq_metric):
             raise vq_exception('predict_with_gradient: the tensors must have as many dimensions as there are characters in "dim_order"')
         t = reshuffle_dims(test.detach(), dim_order, "BCFHW")
         r = reshuffle_dims(reference.detach(), dim_order, "BCFHW")
-        if t.shape[2] != 1 or r.shape[2] != 1:
-            raise vq_exception("predict_with_gradient: video is out of scope, the gradient exists for images (one frame) only")
+        if t.shape[2] != r.shape[2]:
+            raise vq_exception("predict_with_gradient: the reference must have the test's shape (or a batch of 1)")
+        if t.shape[2] > 1:
+            if not frames_per_second > 0:
+                raise vq_exception("predict_with_gradient: a video needs frames_per_second (more than one frame was passed)")
+            fl = hs.temporal_filters(frames_per_second, self.parameters["beta_tf"], self.parameters["sigma_tf"]).shape[1]
+            if fl > _capi.MAX_FILTER_LEN:
+                raise vq_exception(f"frame rates above {(_capi.MAX_FILTER_LEN - 1) * 4} fps are not supported")
+            if t.shape[2] + fl - 1 > _capi.MAX_WINDOW:
+                raise vq_exception(f"predict_with_gradient: the video must be scored as one temporal block, and {t.shape[2]} frames with a filter of {fl} taps "
+                                   f"exceed the window limit CVVDP_MAX_WINDOW = {_capi.MAX_WINDOW} (n_frames + filter_len - 1)")
         if t.shape[1] != 3 or r.shape[1] != 3:
             raise vq_exception("predict_with_gradient: 1-channel content is out of scope, the images must have three colour channels")
         if tuple(t.shape[3:]) != tuple(r.shape[3:]) or (r.shape[0] != t.shape[0] and r.shape[0] != 1):
@@ -579,15 +588,24 @@ class cvvdp(vq_metric):
             raise vq_exception(f"predict_with_gradient: test and reference must be tensors on {self.device}")
         return t, r
 
-    def predict_with_gradient(self, test, reference, dim_order="BCFHW"):
-        """(jod, grad) of an image: `jod` as predict() returns it, `grad` = d jod / d test, float32 on the device, with the shape of
-        `test` in the caller's dim_order; for a batch, grad[b] is the gradient of jod[b] (items do not interact).  float32 tensors on the
-        metric's device, three channels, one frame; sRGB, numeric-gamma and linear displays.  Video, 1-channel content, other dtypes,
-        heat maps, dump_channels and PQ / HLG displays are refused with a vq_exception; there is no gradient for the reference.
-        The backward runs in HIP (cvvdp_image_gradient, csrc/grad.hip) on the pyramid the forward left in the workspace, with torch's
-        subgradient conventions, and gives the same bits on every run.  Images are always scored on the core's unfused route (what
-        fuse_mode = 2 selects for video, as with dump_channels): the JOD is that of predict()."""
-        t, r = self._gradient_inputs(test, reference, dim_order)
+    def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0):
+        """(jod, grad) of an image or of a short clip: `jod` as predict() returns it, `grad` = d jod / d test, float32 on the device, with
+        the shape of `test` in the caller's dim_order; for a batch, grad[b] is the gradient of jod[b] (items do not interact).  float32
+        tensors on the metric's device, three channels; sRGB, numeric-gamma and linear displays.  1-channel content, other dtypes, heat
+        maps, dump_channels and PQ / HLG displays are refused with a vq_exception; there is no gradient for the reference.
+        The backward runs in HIP on the pyramid the forward left in the workspace, with torch's subgradient conventions, and gives the
+        same bits on every run.
+        Images (one frame; cvvdp_image_gradient, csrc/grad.hip) are always scored on the core's unfused route: the JOD is that of predict().
+        Clips (more than one frame, frames_per_second > 0; cvvdp_video_gradient, csrc/grad_video.hip) go through temporal masking and the
+        transient channel, with temp_padding 'replicate' or 'symmetric'.  The clip is scored as ONE temporal block on the unfused route:
+        fuse_mode = 2 and block_frames = n_frames are set for this call and restored, so the JOD is that of predict() with those two
+        settings, and equal to the default predict() to the rounding between the routes.  A clip whose window n_frames + filter_len - 1
+        exceeds CVVDP_MAX_WINDOW (256), or whose workspace and scratch (about 75 bytes per pixel, frame and batch item on top of the
+        forward's 43) cannot be allocated, is refused.  Out of scope: clips longer than one block (a two-pass recompute), file sources,
+        .yuv, --temp-resample, frame sharding."""
+        t, r = self._gradient_inputs(test, reference, dim_order, frames_per_second)
+        if t.shape[2] > 1:
+            return self._predict_video_with_gradient(test, t, r, dim_order, frames_per_second)
         vs = video_source_array(t, r, 0, dim_order="BCFHW", display_photometry=self.display_photometry)
         Q, _, _ = self._score_range(vs, 0, 1)
         jod = self.do_pooling_and_jods(Q)
@@ -605,13 +623,48 @@ class cvvdp(vq_metric):
         del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
         return jod.squeeze(), grad
 
-    def differentiable_loss(self, test, reference, dim_order="BCFHW"):
-        """10 - JOD of an image as a tensor attached to autograd (the reference's loss(): examples/ex_image_reconstruction.py runs with
-        this method's name in place of `loss`).  backward() multiplies the gradient predict_with_gradient() stored by the upstream
-        gradient; the reference receives None, and a reference that requires a gradient is refused."""
+    def _predict_video_with_gradient(self, test, t, r, dim_order, frames_per_second):
+        """predict_with_gradient for a clip: t, r are the BCFHW views on the device."""
+        if self._shard is not None:
+            raise vq_exception("predict_with_gradient: not available with frame sharding")
+        lib = _capi.lib()
+        n_frames = int(t.shape[2])
+        saved = (self.fuse_mode, self.block_frames)
+        self.fuse_mode, self.block_frames = 2, n_frames          # one temporal block on the route that keeps every pyramid level
+        scratch = None
+        try:
+            vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
+            try:
+                Q, _, _ = self._score_range(vs, 0, n_frames)
+                need = int(lib.cvvdp_video_gradient_scratch_bytes(self._handle))
+                scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            except torch.cuda.OutOfMemoryError:
+                ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_scratch_bytes(self._handle))
+                self._ws = None
+                raise vq_exception(f"predict_with_gradient: the clip needs a workspace of {ws} bytes and a scratch of {sc} bytes as one temporal block, "
+                                   "which cannot be allocated on this device") from None
+            jod = self.do_pooling_and_jods(Q)
+            grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
+            gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
+            assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
+            st = (ctypes.c_int64 * 5)(*t.stride())
+            sg = (ctypes.c_int64 * 5)(*gv.stride())
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = lib.cvvdp_video_gradient(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(), scratch.numel(), stream)
+            _capi.check(self._handle, rc, "cvvdp_video_gradient")
+        finally:
+            self.fuse_mode, self.block_frames = saved
+            del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
+        return jod.squeeze(), grad
+
+    def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0):
+        """10 - JOD of an image or a short clip as a tensor attached to autograd (the reference's loss(): examples/ex_image_reconstruction.py
+        runs with this method's name in place of `loss`).  backward() multiplies the gradient predict_with_gradient() stored by the
+        upstream gradient, one factor per batch item; the reference receives None, and a reference that requires a gradient is refused.
+        Clips: see predict_with_gradient."""
         if torch.is_tensor(reference) and reference.requires_grad:
             raise vq_exception("differentiable_loss: a gradient for the reference is out of scope")
-        return _JodLoss.apply(test, reference, self, dim_order)
+        return _JodLoss.apply(test, reference, self, dim_order, frames_per_second)
 
     def predict_video_source(self, vid_source, heatmap_sink=None):
         """cvvdp_metric.py:304-441.

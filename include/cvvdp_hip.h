@@ -482,6 +482,31 @@ size_t cvvdp_image_gradient_scratch_bytes(const cvvdp_handle* h);
 int cvvdp_image_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                          size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* Gradient of the VIDEO JOD with respect to the test clip: dev_grad[b] = d JOD[b] / d test[b], through temporal masking and the
+ * transient channel.  Valid on a video clip of three channels configured without heat map, features and defer_bands, with
+ * block_frames >= n_frames and on the unfused route (fuse_mode = 2: cvvdp_fused_levels(h) == 0), after the cvvdp_process_block that
+ * scored all n_frames frames (frame offset 0, raw_first 0, dtype CVVDP_F32, every hist_src entry a frame of the clip): the handle
+ * remembers that call's padding map.  The Gaussian levels of all 2 x 4 temporal-channel planes of every frame and Q_per_ch are read
+ * from the workspace, which must not have been touched since.  Displays as for cvvdp_image_gradient; batch items do not interact.
+ *   dev_test       the fp32 test frames that cvvdp_process_block was given, with their element strides (B, C, F, H, W)
+ *   dev_grad       fp32, written through strides_grad (same order, every stride >= 0): B x 3 x n_frames x H x W samples; the last one
+ *                  must lie inside grad_bytes
+ *   dev_scratch    cvvdp_video_gradient_scratch_bytes(h) bytes, 16-byte aligned (the size of the CONFIGURED clip; 0 where the clip is
+ *                  not one the gradient exists for).  In floats, every part rounded up to 64, with items = n_frames * batch and P_l the
+ *                  pixels of level l: coef items * 4 * L; the FIR weight table 4 * n_frames^2; three temporaries of 4 * items * P_0;
+ *                  per level 4 * items * P_l, and items * P_l more on all but the last.  About 18.7 floats (75 bytes) per pixel, frame
+ *                  and batch item: 1080p x 16 frames needs 2.5 GB
+ * The pooling over frames is differentiated in float64 by a kernel; the band chain is that of cvvdp_image_gradient with four channels
+ * over frames x batch items; the adjoint of the temporal FIR, with replicate or symmetric padding, is fused with the display model's
+ * (d JOD / d DKL never touches memory).  Every kernel is a gather or a per-thread serial walk without atomics: the same bits on every
+ * run.  Nothing synchronises.  Argument errors (null pointer, misaligned pointer, negative stride, short gradient buffer or scratch) give
+ * CVVDP_E_ARG; 1 channel, heat map, features, PQ / HLG, or more than 65535 / 4 frames x batch items CVVDP_E_UNSUPPORTED; an image clip,
+ * defer_bands, block_frames < n_frames, a fused route, or a call before the whole clip was scored CVVDP_E_STATE -- all before any
+ * launch.  Added; nothing else changed, so CVVDP_ABI_VERSION stays 14. */
+size_t cvvdp_video_gradient_scratch_bytes(const cvvdp_handle* h);
+int cvvdp_video_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
+                         size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
