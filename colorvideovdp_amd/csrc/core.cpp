@@ -1203,6 +1203,80 @@ int cvvdp::grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t s
   return CVVDP_OK;
 }
 int cvvdp::grad_video_check_launch(cvvdp_handle* h) { return check_launch(h, "video_gradient"); }
+// cvvdp_param_gradient (grad_param.hip) up to the launches.  The caller's scratch, every part on a 256-byte granule, sized for a full
+// block (items = block_frames * batch; 1 * batch for an image) of NC = 3 / 4 channels: coef [items][NC][L] floats; two temporaries
+// [NC][items][P0] floats; the slab [batch][block_frames * R][24] doubles, R = sum over the Laplacian levels of ceil(P_l / 2048), + 1
+namespace {
+struct ParamLayout { size_t coef, t[2], slab, total; int nblk[CVVDP_MAX_LEVELS], row_off[CVVDP_MAX_LEVELS], rows_frame; };
+bool param_clip_ok(const cvvdp_handle* h) {
+  if (!h || !h->configured) return false;
+  const cvvdp_clip& c = h->c;
+  return c.channels == 3 && c.heatmap == CVVDP_HEATMAP_NONE && c.feature_size <= 0 && !c.defer_bands &&
+         (!c.is_video || (h->fuse_levels == 0 && !h->pipeline)) && (int64_t)h->items_cap * h->nch <= 65535;
+}
+ParamLayout param_layout(const cvvdp_handle* h) {
+  ParamLayout g{};
+  const size_t items = (size_t)h->items_cap, NC = (size_t)h->nch;
+  size_t off = 0;
+  g.coef = off; off += align_up(items * NC * h->L);
+  for (int k = 0; k < 2; ++k) { g.t[k] = off; off += align_up(NC * items * (size_t)h->lv[0].P); }
+  int rows = 0;
+  for (int l = 0; l < h->L; ++l) {
+    g.nblk[l] = l + 1 < h->L ? (int)((h->lv[l].P + CVVDP_PARAM_BLOCK_PX - 1) / CVVDP_PARAM_BLOCK_PX) : 1;
+    g.row_off[l] = rows; rows += g.nblk[l];
+  }
+  g.rows_frame = rows;
+  g.slab = off; off += align_up(items * (size_t)rows * CVVDP_PARAM_GRAD_COUNT * 2);      // (doubles: two floats each)
+  g.total = off;
+  return g;
+}
+}  // namespace
+size_t cvvdp::param_grad_scratch(const cvvdp_handle* h) { return param_clip_ok(h) ? param_layout(h).total * sizeof(float) : 0; }
+int cvvdp::param_grad_prepare(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, ParamPlan& plan) {
+  if (!h) return CVVDP_E_STATE;
+  if (!dq || !acc || !scratch) return fail(h, CVVDP_E_ARG, "param_gradient: null argument");
+  if (reinterpret_cast<uintptr_t>(dq) % 4 || reinterpret_cast<uintptr_t>(acc) % 8 || reinterpret_cast<uintptr_t>(scratch) % 16)
+    return fail(h, CVVDP_E_ARG, "param_gradient: dq must be 4-byte aligned, acc 8-byte aligned, the scratch 16-byte aligned");
+  if (!h->configured) return fail(h, CVVDP_E_STATE, "param_gradient: configure first");
+  const cvvdp_clip& c = h->c;
+  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "param_gradient: 1-channel content is out of scope");
+  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "param_gradient: not with a heat map or features");
+  if (c.defer_bands) return fail(h, CVVDP_E_STATE, "param_gradient: not for clips scored in pieces (defer_bands)");
+  if (c.is_video && (h->fuse_levels != 0 || h->pipeline))
+    return fail(h, CVVDP_E_STATE, "param_gradient: needs the unfused route (fuse_mode = 2), which keeps every pyramid level in the workspace");
+  const int NC = h->nch, L = h->L, B = c.batch;
+  if ((int64_t)h->items_cap * NC > 65535)      // (NC planes per item in a grid's y)
+    return fail(h, CVVDP_E_UNSUPPORTED, "param_gradient: %d frames x %d batch items are too many (%d planes per item, 65535 at most)",
+                c.is_video ? c.block_frames : 1, B, NC);
+  const ParamLayout lay = param_layout(h);
+  if (scratch_bytes < lay.total * sizeof(float))
+    return fail(h, CVVDP_E_ARG, "param_gradient: scratch of %zu bytes, %zu needed", scratch_bytes, lay.total * sizeof(float));
+  if (!h->ws || h->last_items < 1 || h->last_item0 != 0 || h->last_items % B != 0 || (!c.is_video && !h->image_scored))
+    return fail(h, CVVDP_E_STATE, c.is_video ? "param_gradient: valid after a cvvdp_process_block" : "param_gradient: valid after cvvdp_put_image and cvvdp_process_image");
+  float* sc = static_cast<float*>(scratch);
+  const int items = h->last_items, n_frames = items / B;
+  plan = ParamPlan{};
+  plan.NC = NC; plan.L = L; plan.items = items;
+  ParamCoefArgs& co = plan.coef;
+  co.dq = dq; co.q = h->ws + h->q_off; co.coef = sc + lay.coef;
+  co.B = B; co.NC = NC; co.count = c.n_frames; co.L = L; co.n_frames = n_frames; co.q0 = h->last_q0;
+  for (int l = 0; l < L; ++l) co.n_px[l] = (int32_t)h->lv[l].P;
+  // the chain's arguments; of its three temporaries the third, the per-level outputs and the pyramid adjoints are not used here
+  const size_t t[3] = {lay.t[0], lay.t[1], lay.t[0]};
+  const size_t none[CVVDP_MAX_LEVELS] = {};
+  GradAccumArgs unused[CVVDP_MAX_LEVELS];
+  if (NC == 3) fill_grad_chain<3>(h, items, sc, t, none, none, co.coef, plan.band3, plan.base3, unused);
+  else fill_grad_chain<4>(h, items, sc, t, none, none, co.coef, plan.band4, plan.base4, unused);
+  double* slab = reinterpret_cast<double*>(sc + lay.slab);
+  const int64_t rows_b = (int64_t)lay.rows_frame * n_frames;
+  for (int l = 0; l < L; ++l) {
+    ParamRowArgs& r = plan.rows[l];
+    r.slab = slab; r.rows_b = rows_b; r.row_off = lay.row_off[l]; r.nblk = lay.nblk[l]; r.n_frames = n_frames; r.B = B;
+  }
+  plan.red.slab = slab; plan.red.acc = acc; plan.red.rows_b = rows_b;
+  return CVVDP_OK;
+}
+int cvvdp::param_grad_check_launch(cvvdp_handle* h) { return check_launch(h, "param_gradient"); }
 // cvvdp_pixel_preview (preview.hip) up to the launch: the source checks of cvvdp_pixel_sse on one side, then the target, the format and
 // the canvas.  Nothing is launched unless the last pixel of the last frame lies inside dst_bytes.
 int cvvdp::preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref,

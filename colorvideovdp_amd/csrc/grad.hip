@@ -174,6 +174,13 @@ void launch_grad_chain4(int L, int items, const GradBandArgsT<4>* band, const Gr
   launch_chain<4>(L, items, band, base, acc, s);
 }
 
+// the parameter gradient (grad_param.hip) runs the first steps of a level's chain: the same kernels, launched as launch_chain does
+void launch_grad_min3(const GradBandArgsT<3>& a, hipStream_t s) { hipLaunchKernelGGL(k_grad_min<3>, pixel_grid(a.H, a.W, a.B), dim3(GT), 0, s, a); }
+void launch_grad_min4(const GradBandArgsT<4>& a, hipStream_t s) { hipLaunchKernelGGL(k_grad_min<4>, pixel_grid(a.H, a.W, a.B), dim3(GT), 0, s, a); }
+void launch_grad_blur_fwd(const float* in, float* out, int H, int W, int planes, bool vertical, const float* w, hipStream_t s) {
+  blur_pass(in, out, H, W, planes, vertical, false, w, s);
+}
+
 }  // namespace cvvdp
 
 // ---------------------------------------------------------------- C ABI (include/cvvdp_hip.h)

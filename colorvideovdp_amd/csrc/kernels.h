@@ -716,4 +716,41 @@ int grad_video_check_launch(cvvdp_handle* h);
 void launch_grad_chain4(int L, int items, const GradBandArgsT<4>* band, const GradBaseArgsT<4>& base, const GradAccumArgs* acc, hipStream_t s);
 void launch_video_gradient(const GradVideoPlan& p, hipStream_t s);
 
+// ---------------------------------------------------------------- gradient of the JOD in the model's parameters (grad_param.hip, grad_param_dev.h)
+// d JOD[b] / d (mask_p, mask_c, mask_q, xcm_weights, d_max, sensitivity_correction) of the block processed last, added to acc [B][24].
+// Per Laplacian level: k_grad_min and the forward blur of the chain above, then one per-pixel kernel whose blocks each leave a row of 24
+// float64 partial sums in a slab; the baseband leaves one row per item; k_param_reduce adds a batch item's rows in a fixed order.
+constexpr int CVVDP_PARAM_BLOCK_PX = 2048;   // pixels per block of k_param_point: 256 threads x 8 (a grid-stride loop keeps the slab small)
+constexpr int CVVDP_PARAM_LANES = 32;        // k_param_reduce: row r of a batch item goes to lane group r % 32, the groups are added in ascending order
+struct ParamCoefArgs {       // dJOD/dQ_per_ch (from the host's float64 pooling) -> coef of the band chain: dq / (N_l (Q + sqrt(eps)))
+  const float* dq;          // [B][NC][count][L], the layout of cvvdp_get_q_per_ch
+  const float* q;           // Q_per_ch, same layout
+  float* coef;              // [n_frames * B][NC][L], item = frame * B + b
+  int32_t B, NC, count, L, n_frames, q0;
+  int32_t n_px[CVVDP_MAX_LEVELS];
+};
+struct ParamRowArgs {        // where the blocks of one level put their rows: slab[b][row_off * n_frames + f * nblk + blk][24]
+  double* slab;
+  int64_t rows_b;           // rows per batch item (the block's n_frames x rows per frame)
+  int32_t row_off, nblk, n_frames, B;
+};
+struct ParamReduceArgs { const double* slab; double* acc; int64_t rows_b; };
+struct ParamPlan {           // everything cvvdp_param_gradient launches, filled by core.cpp
+  int32_t NC, L, items;
+  ParamCoefArgs coef;
+  GradBandArgsT<3> band3[CVVDP_MAX_LEVELS];
+  GradBandArgsT<4> band4[CVVDP_MAX_LEVELS];
+  GradBaseArgsT<3> base3;
+  GradBaseArgsT<4> base4;
+  ParamRowArgs rows[CVVDP_MAX_LEVELS];
+  ParamReduceArgs red;
+};
+size_t param_grad_scratch(const cvvdp_handle* h);
+int param_grad_prepare(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, ParamPlan& plan);
+int param_grad_check_launch(cvvdp_handle* h);
+// grad.hip: k_grad_min and one forward pass of the 13-tap blur, as the pixel gradient's chain launches them
+void launch_grad_min3(const GradBandArgsT<3>& a, hipStream_t s);
+void launch_grad_min4(const GradBandArgsT<4>& a, hipStream_t s);
+void launch_grad_blur_fwd(const float* in, float* out, int H, int W, int planes, bool vertical, const float* w, hipStream_t s);
+
 }  // namespace cvvdp

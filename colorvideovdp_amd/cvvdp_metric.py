@@ -281,6 +281,80 @@ class _JodLoss(torch.autograd.Function):
         return -grad * up, None, None, None, None
 
 
+_CSF_TABLES = {}
+
+
+def _csf_table(config_paths):
+    """hs.CsfTable of csf_lut_weber_fixed_size.json, made once per resolved file (a file on disk: per path, size and modification time):
+    a calibration step assigns parameters, and _set_parameters must not parse the table again for each."""
+    import os
+    path = config_files.find("csf_lut_weber_fixed_size.json", config_paths)
+    key = path
+    if not path.startswith("builtin:"):
+        st = os.stat(path)
+        key = (os.path.abspath(path), st.st_size, st.st_mtime_ns)
+    table = _CSF_TABLES.get(key)
+    if table is None:
+        table = _CSF_TABLES[key] = hs.CsfTable(json2dict(path))
+    return table
+
+
+# the parameters predict_with_parameter_gradient() differentiates in, as the parameter file names them: the band stage's (24 sums of
+# cvvdp_param_gradient, in the order of its slots) and the pooling stage's (pool_jod_float64 under autograd)
+BAND_PARAMETERS = {"mask_p": (0, 1), "mask_c": (1, 2), "mask_q": (2, 6), "xcm_weights": (6, 22), "d_max": (22, 23), "sensitivity_correction": (23, 24)}
+POOLING_PARAMETERS = ("ch_chrom_w", "ch_trans_w", "baseband_weight", "jod_a", "jod_exp", "image_int")
+GRADIENT_PARAMETERS = tuple(BAND_PARAMETERS) + POOLING_PARAMETERS
+
+
+def pool_jod_float64(Q_per_ch, ch_chrom_w, ch_trans_w, baseband_weight, jod_a, jod_exp, image_int, beta_sch, beta_tch, beta_t):
+    """do_pooling_and_jods (cvvdp_metric.py:610-658) restated in float64 torch, differentiable in Q_per_ch [B, C, F, L] and in the six
+    pooling parameters: lp_norm with safe_pow over bands, channels and (clips: normalised) frames, image_int for one frame, both
+    branches of met2jod.  A parameter may carry a leading batch dimension ([B] or [B, 4]): row b then acts on item b alone, which is how
+    one autograd call yields d JOD[b] / d parameter for every b.  Runs on CPU tensors as well.  Returns JOD [B], float64."""
+    Q = Q_per_ch.double()
+    B, C, F, L = Q.shape
+    eps = 1e-5
+    two = lambda x, n: torch.as_tensor(x, device=Q.device).double().reshape(-1, n)        # [1 or B, n]
+    spow = lambda x, p: (x + eps) ** p - eps ** p
+    cw, tw, bw = two(ch_chrom_w, 1), two(ch_trans_w, 1), two(baseband_weight, 4)
+    n = max(cw.shape[0], tw.shape[0], bw.shape[0])
+    one = torch.ones((n, 1), dtype=torch.float64, device=Q.device)
+    chw = torch.cat([one, cw.expand(n, 1), cw.expand(n, 1), tw.expand(n, 1)], dim=1)[:, :C].reshape(n, C, 1, 1)
+    wb = torch.cat([one[:, :, None].expand(n, C, L - 1), bw.expand(n, 4)[:, :C, None]], dim=2).reshape(n, C, 1, L)
+    bs, bt, bf = float(beta_sch), float(beta_tch), float(beta_t)
+    Qsc = spow(spow(Q * chw * wb, bs).sum(dim=3), 1.0 / bs)                                # [B, C, F]
+    Qtc = spow(spow(Qsc, bt).sum(dim=1), 1.0 / bt)                                        # [B, F]
+    if F == 1:
+        Qv = Qtc[:, 0] * two(image_int, 1)[:, 0]
+    else:
+        Qv = spow(spow(Qtc, bf).sum(dim=1) / F, 1.0 / bf)
+    a, e, Qt = two(jod_a, 1)[:, 0], two(jod_exp, 1)[:, 0], 0.1
+    lin = 10.0 - a * Qt ** (e - 1.0) * Qv
+    pw = 10.0 - a * torch.clamp(Qv, min=Qt) ** e
+    return torch.where(Qv <= Qt, lin, pw)
+
+
+class _ParamJod(torch.autograd.Function):
+    """JOD with the gradient of cvvdp.predict_with_parameter_gradient in the tensors of P (cvvdp.differentiable_jod)."""
+
+    @staticmethod
+    def forward(ctx, metric, test, reference, dim_order, frames_per_second, names, *tensors):
+        jod, grads = metric.predict_with_parameter_gradient(test, reference, dim_order, frames_per_second)
+        ctx.names = names
+        ctx.shapes = [tuple(t.shape) for t in tensors]
+        ctx.targets = [(t.device, t.dtype) for t in tensors]
+        ctx.save_for_backward(*[grads[n] for n in names])
+        return jod
+
+    @staticmethod
+    def backward(ctx, upstream):
+        out = []
+        for g, shape, (dev, dt) in zip(ctx.saved_tensors, ctx.shapes, ctx.targets):
+            up = upstream.reshape(-1).to(g.dtype).reshape((-1,) + (1,) * (g.dim() - 1))      # one factor per batch item
+            out.append((up * g).sum(dim=0).reshape(shape).to(dev, dt))
+        return (None,) * 6 + tuple(out)
+
+
 class cvvdp(vq_metric):
     def __init__(self, display_name="standard_4k", display_photometry=None, display_geometry=None, config_paths=[],
                  heatmap=None, quiet=False, device=None, temp_padding="replicate", use_checkpoints=False, dump_channels=None,
@@ -418,7 +492,7 @@ class cvvdp(vq_metric):
             d["parameters"] = p
             d["version"] = p["version"]
             d["pu_dilate"] = p["pu_dilate"]
-            d["csf_table"] = hs.CsfTable(load_config("csf_lut_weber_fixed_size.json", self._config_paths))
+            d["csf_table"] = _csf_table(self._config_paths)
             d["_jod_a"], d["_jod_exp"] = f32(p["jod_a"]), f32(p["jod_exp"])
             d["_baseband_weight"] = np.asarray(p["baseband_weight"], dtype=f32)
             d["_ch_w"] = np.asarray([1.0, p["ch_chrom_w"], p["ch_chrom_w"], p["ch_trans_w"]], dtype=f32)
@@ -666,6 +740,140 @@ class cvvdp(vq_metric):
             raise vq_exception("differentiable_loss: a gradient for the reference is out of scope")
         return _JodLoss.apply(test, reference, self, dim_order, frames_per_second)
 
+    # ------------------------------------------------------------------ gradient in the model's parameters (calibration)
+    @staticmethod
+    def _gradient_names(names):
+        names = GRADIENT_PARAMETERS if names is None else tuple(names)
+        for n in names:
+            if n not in GRADIENT_PARAMETERS:
+                raise vq_exception(f"unknown parameter '{n}': the parameter gradient exists for {', '.join(GRADIENT_PARAMETERS)}")
+        return names
+
+    def parameter_tensors(self, names=None):
+        """name -> float32 leaf tensor (requires_grad) on the metric's device with the parameter's current value as the parameter file
+        stores it (mask_c and d_max as exponents of 10, xcm_weights as exponents of 2, sensitivity_correction in dB): what
+        differentiable_jod() takes and an optimiser steps.  names: a subset of cvvdp_metric.GRADIENT_PARAMETERS (None: all twelve)."""
+        dev = self._param_device()
+        return {n: torch.tensor(self.parameters[n], dtype=torch.float32, device=dev).requires_grad_(True) for n in self._gradient_names(names)}
+
+    def _parameter_gradient_refusals(self, what, vs=None):
+        if self.do_heatmap:
+            raise vq_exception(f"{what}: not available with a heat map")
+        if self.dump_channels is not None:
+            raise vq_exception(f"{what}: not available with dump_channels")
+        if getattr(self, "_feature_out", None) is not None:
+            raise vq_exception(f"{what}: not available with extract_features")
+        if self._shard is not None:
+            raise vq_exception(f"{what}: not available with frame sharding")
+        if vs is not None and hasattr(vs, "set_temporal_filters"):
+            raise vq_exception(f"{what}: sources that filter in time themselves (--temp-resample) are out of scope")
+        if isinstance(vs, video_source_array) and vs.raw_arrays()[0].shape[1] != 3:
+            raise vq_exception(f"{what}: 1-channel content is out of scope, the content must have three colour channels")
+
+    def predict_with_parameter_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0):
+        """(jod, grads) of an image or a clip: grads[name] = d jod[b] / d parameter `name`, float32 on the device, shape
+        [B, *shape of the parameter], for the twelve parameters of cvvdp_metric.GRADIENT_PARAMETERS as the parameter file stores them.
+        Accepts what predict() accepts with three colour channels; see predict_video_source_with_parameter_gradient."""
+        vs = video_source_array(test, reference, frames_per_second, dim_order=dim_order, display_photometry=self.display_photometry)
+        return self.predict_video_source_with_parameter_gradient(vs)
+
+    def predict_video_source_with_parameter_gradient(self, vid_source):
+        """(jod, grads) of any source predict_video_source() scores block by block (arrays of every dtype, .yuv and image files, every
+        display, both paddings, clips of any length).  `jod` is do_pooling_and_jods of the scored Q_per_ch: predict() with fuse_mode = 2,
+        bit for bit (the call sets fuse_mode = 2 for itself and restores it).  The pooling parameters' gradients and dJOD/dQ_per_ch come
+        from pool_jod_float64 under autograd; the band parameters' from cvvdp_param_gradient (csrc/grad_param.hip) after every block.
+        Pooling over frames couples the frames, so a clip of several blocks is walked twice (a file source is read twice); an image or a
+        clip of one block is scored once.  Entries that cannot act are exactly 0 (images: ch_trans_w, mask_q[3], baseband_weight[3],
+        xcm_weights[4 k + c] with k = 3 or c = 3; clips: image_int).  Heat maps, dump_channels, extract_features, frame sharding,
+        1-channel content and sources that filter in time themselves are refused with a vq_exception."""
+        what = "predict_with_parameter_gradient"
+        inner = getattr(vid_source, "vs", None)             # (as predict_video_source)
+        if isinstance(inner, video_source):
+            vid_source = inner
+        self._parameter_gradient_refusals(what, vid_source)
+        if not torch.cuda.is_available():
+            raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
+        src_dm = getattr(vid_source, "dm_photometry", None)
+        swap = src_dm is not None and src_dm is not self.display_photometry and self._is_raw_source(vid_source)
+        prev_dm = self.display_photometry
+        saved = self.fuse_mode
+        if swap:
+            self.display_photometry = src_dm
+            self._make_handle()
+        self.fuse_mode, self._param_grad_plan = 2, True
+        try:
+            return self._parameter_gradient(vid_source, what)
+        finally:
+            self.fuse_mode, self._param_grad_plan, self._block_hook = saved, False, None
+            if swap:
+                self.display_photometry = prev_dm
+                self._make_handle()
+
+    def _parameter_gradient(self, vs, what):
+        lib = _capi.lib()
+        _h, _w, n_frames = vs.get_video_size()
+        Q, _, _ = self._score_range(vs, 0, n_frames)                       # pass 1: the normal block loop
+        if self._route_channels != 3:
+            raise vq_exception(f"{what}: 1-channel content is out of scope, the content must have three colour channels")
+        jod = self.do_pooling_and_jods(Q)
+        B = int(Q.shape[0])
+        p = self.parameters
+        # the pooling stage in float64 on the host (a few thousand numbers): its parameters' gradients and dJOD/dQ_per_ch in one autograd call
+        Qh = Q.detach().to("cpu", torch.float64).requires_grad_(True)
+        leaves = {n: torch.tensor(p[n], dtype=torch.float64).reshape(1, -1).repeat(B, 1).requires_grad_(True) for n in POOLING_PARAMETERS}
+        with torch.enable_grad():
+            j64 = pool_jod_float64(Qh, beta_sch=p["beta_sch"], beta_tch=p["beta_tch"], beta_t=p["beta_t"], **leaves)
+            got = torch.autograd.grad(j64.sum(), [Qh] + [leaves[n] for n in POOLING_PARAMETERS], allow_unused=True)
+        dq = got[0].to(torch.float32).to(self.device).contiguous()
+        grads = {}
+        for n, g in zip(POOLING_PARAMETERS, got[1:]):
+            g = torch.zeros_like(leaves[n]) if g is None else g
+            grads[n] = g.to(torch.float32).reshape((B,) + tuple(np.shape(p[n]))).to(self.device)
+        # the band stage: 24 sums per batch item, added block by block
+        acc = torch.zeros((B, _capi.PARAM_GRAD_COUNT), dtype=torch.float64, device=self.device)
+        try:
+            scratch = torch.empty(max(int(lib.cvvdp_param_gradient_scratch_bytes(self._handle)), 16), dtype=torch.uint8, device=self.device)
+        except torch.cuda.OutOfMemoryError:
+            raise vq_exception(f"{what}: the scratch of {int(lib.cvvdp_param_gradient_scratch_bytes(self._handle))} bytes cannot be allocated on this device") from None
+
+        def after_block(stream):
+            rc = lib.cvvdp_param_gradient(self._handle, dq.data_ptr(), acc.data_ptr(), scratch.data_ptr(), scratch.numel(), stream)
+            _capi.check(self._handle, rc, "cvvdp_param_gradient")
+
+        if n_frames == 1 or n_frames <= int(self.last_block_frames):
+            after_block(torch.cuda.current_stream(self.device).cuda_stream)     # one block: its pyramid is still in the workspace
+        else:
+            self._block_hook = after_block                                      # pass 2: the same blocks again, the entry after each
+            try:
+                self._score_range(vs, 0, n_frames)
+            finally:
+                self._block_hook = None
+        band = acc.to(torch.float32)
+        for n, (a, b) in BAND_PARAMETERS.items():
+            grads[n] = band[:, a:b].reshape((B,) + tuple(np.shape(p[n]))).contiguous()
+        del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
+        return jod.squeeze(), {n: grads[n] for n in GRADIENT_PARAMETERS}
+
+    def differentiable_jod(self, test, reference, P, dim_order="BCFHW", frames_per_second=0):
+        """JOD attached to autograd in the parameter tensors of P (name -> tensor, as parameter_tensors() makes them): the values of P are
+        installed in the metric if they differ from its own (all or nothing, through the path every parameter assignment takes; names
+        absent from P keep their values), the content is scored, and backward() adds upstream[b] x d jod[b] / d parameter, summed over
+        b, to every tensor of P.  test and reference must not require a gradient (differentiable_loss() is the pixel side)."""
+        for a in (test, reference):
+            if torch.is_tensor(a) and a.requires_grad:
+                raise vq_exception("differentiable_jod: a gradient for test or reference is out of scope here (differentiable_loss() gives the pixel gradient)")
+        names = self._gradient_names(list(P.keys()))
+        self._parameter_gradient_refusals("differentiable_jod")
+        q = dict(self.parameters)
+        changed = False
+        for n in names:
+            v = self._parameter_value(n, P[n], q[n])
+            if not np.array_equal(np.asarray(v, dtype=f32), np.asarray(q[n], dtype=f32)):
+                q[n], changed = v, True
+        if changed:
+            self._set_parameters(q)
+        return _ParamJod.apply(self, test, reference, dim_order, frames_per_second, names, *[P[n] for n in names])
+
     def predict_video_source(self, vid_source, heatmap_sink=None):
         """cvvdp_metric.py:304-441.
 
@@ -796,6 +1004,8 @@ class cvvdp(vq_metric):
             if self.dump_channels is not None:
                 # the per-pixel D of every band (4 planes with their pyramid) and the 8-bit canvases: 2H x 2W, and two of about 2H x 3W
                 per_frame += pix * batch * 4 * 4 * 1.34 + pix * 3 * (4 + 6 + 6) * 1.1
+            if getattr(self, "_param_grad_plan", False):
+                per_frame += pix * batch * (2 * nch * 4 + 1)      # cvvdp_param_gradient's scratch: two temporaries of nch planes and the slab of row sums
             fixed = pix * batch * 24 * (fl - 1)
             nb = int((budget - fixed) // per_frame)
             # heat maps leave the GPU over PCIe (2-6 B/pixel): 16-frame blocks let the copy of a block overlap the
@@ -934,6 +1144,7 @@ class cvvdp(vq_metric):
         else:
             probe_t, probe_r, code = self._raw_block(vs, first, first + 1)
             C = probe_t.shape[1]
+        self._route_channels = C
         return _Route(height, width, n_total, vs.get_batch_size(), L, rho_band, is_image, is_yuv, yuv_resized, generic, prefiltered,
                       3 if is_image else 4, C, code, probe_t, probe_r)
 
@@ -944,7 +1155,7 @@ class cvvdp(vq_metric):
         height, width, is_image, prefiltered = rt.height, rt.width, rt.is_image, rt.prefiltered
         key = (height, width, rt.n_total, first, count, rt.B, rt.C, is_image, None if is_image else float(vs.get_frames_per_second()), self.heatmap,
                bool(self.debug_dump or self.dump_channels is not None), int(self.fuse_mode), int(self.band_layout), self.score_frames, self._sink_on_device, self.block_frames, self.gpu_mem, float(self.pix_per_deg), self._cfg_version, prefiltered, getattr(self, "_feature_out", None) is not None,
-               self._host_resident(vs))
+               self._host_resident(vs), bool(getattr(self, "_param_grad_plan", False)))
         cached = getattr(self, "_clip_cache", None)
         if cached is not None and cached[0] == key:
             clip, fl, F = cached[1], cached[2], cached[3]
@@ -1091,6 +1302,8 @@ class cvvdp(vq_metric):
             rc = _capi.lib().cvvdp_process_block_filtered(self._handle, t.data_ptr(), r.data_ptr(), st, sr, n, ff - first, stream)
             _capi.check(self._handle, rc, "cvvdp_process_block_filtered")
             self._fetch_outputs(rt, out, ff - first, n, stream)
+            if getattr(self, "_block_hook", None) is not None:
+                self._block_hook(stream)
             del t, r
 
     def _run_blocks(self, vs, rt, clip, blocks, first, out, stream):
@@ -1114,6 +1327,8 @@ class cvvdp(vq_metric):
                         _capi.check(self._handle, lib.cvvdp_score_frames(self._handle, p0, m, stream), "cvvdp_score_frames")
                         out.fetch(ff - first + p0, m)
                 self._fetch_outputs(rt, out, ff - first, n, stream, heatmap=not clip.defer_bands)
+                if getattr(self, "_block_hook", None) is not None:      # the second pass of predict_with_parameter_gradient
+                    self._block_hook(stream)
                 del t, r  # stream-ordered: safe to release to the caching allocator once the kernels are queued
         finally:
             fetched.close()     # (joins the upload worker, also when a block raised)

@@ -507,6 +507,33 @@ size_t cvvdp_video_gradient_scratch_bytes(const cvvdp_handle* h);
 int cvvdp_video_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                          size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* Gradient of the JOD in the model's PARAMETERS, for calibration: dev_acc[b][j] += d JOD[b] / d parameter j over the frames of the block
+ * processed last, with the parameters as the parameter file stores them (mask_c and d_max as exponents of 10, xcm_weights as exponents
+ * of 2, sensitivity_correction in dB).  Slots j: 0 mask_p, 1 mask_c, 2..5 mask_q[0..3], 6..21 xcm_weights[0..15], 22 d_max,
+ * 23 sensitivity_correction; slots of a channel an image does not have (mask_q[3], xcm_weights[4 k + c] with k = 3 or c = 3) receive
+ * exactly 0.  The pooling parameters (ch_chrom_w, ch_trans_w, baseband_weight, jod_a, jod_exp, image_int) act on Q_per_ch alone and are
+ * the caller's (colorvideovdp_amd.cvvdp_metric.pool_jod_float64).
+ *   dev_dq         fp32 d JOD / d Q_per_ch in the layout of cvvdp_get_q_per_ch, [B][C][n_frames][bands] of the CONFIGURED range; the entry
+ *                  reads the frames of the block processed last (it knows that block's n_frames and q_frame_offset).  Pooling over frames
+ *                  couples the frames, so this is known only once the whole clip is scored: a clip of several blocks is walked twice
+ *   dev_acc        [B][CVVDP_PARAM_GRAD_COUNT] doubles; the entry ADDS to it, the caller zeroes it before the first block
+ *   dev_scratch    cvvdp_param_gradient_scratch_bytes(h) bytes, 16-byte aligned (the size of the CONFIGURED clip, 0 where the clip is not
+ *                  one the entry exists for).  In floats, every part rounded up to 64, with items = block_frames * batch (images: batch),
+ *                  NC = 4 (images: 3) and P_l the pixels of level l: coef items * NC * bands; two temporaries of NC * items * P_0; the
+ *                  slab of row sums, items * R * 24 doubles with R = sum over the Laplacian levels of ceil(P_l / 2048), + 1 for the
+ *                  baseband.  About 32 bytes per pixel, frame and batch item (images: 24)
+ * Valid after cvvdp_put_image + cvvdp_process_image, and after a cvvdp_process_block / cvvdp_process_block_yuv of ANY input type on the
+ * unfused route (fuse_mode = 2: cvvdp_fused_levels(h) == 0); block_frames < n_frames is allowed, and every display (nothing flows through
+ * the EOTF or the temporal filter).  The Gaussian levels of the block and Q_per_ch are read from the workspace, which must not have been
+ * touched since.  Per level: min(|T'|, |R'|), the forward 13 x 13 blur, one per-pixel kernel; the per-pixel terms are float32, every sum
+ * over pixels, blocks, frames and levels is float64 in a fixed order without atomics: the same bits on every run for the same block plan,
+ * and a batch item's sums equal the item's alone.  Nothing synchronises.  Null or misaligned pointers and a short scratch give
+ * CVVDP_E_ARG; 1 channel, heat map, features, or more than 65535 / NC items per block CVVDP_E_UNSUPPORTED; defer_bands, a fused route, or
+ * a call before a block was processed CVVDP_E_STATE -- all before any launch.  Added; nothing else changed, so CVVDP_ABI_VERSION stays 14. */
+#define CVVDP_PARAM_GRAD_COUNT 24   /* mask_p, mask_c, mask_q[0..3], xcm_weights[0..15], d_max, sensitivity_correction */
+size_t cvvdp_param_gradient_scratch_bytes(const cvvdp_handle* h);
+int cvvdp_param_gradient(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
