@@ -190,6 +190,10 @@ SYMBOLS = {
     "cvvdp_video_gradient_scratch_bytes": (C.c_size_t, [C.c_void_p]),
     "cvvdp_video_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_video_gradient_blocks_scratch_bytes": (C.c_size_t, [C.c_void_p]),
+    "cvvdp_video_gradient_blocks_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_video_gradient_block": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_param_gradient_scratch_bytes": (C.c_size_t, [C.c_void_p]),
     "cvvdp_param_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_preview_args_size": (C.c_int32, []),

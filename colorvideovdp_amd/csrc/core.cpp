@@ -79,6 +79,12 @@ struct cvvdp_handle {
   // on, and the padding map it was given (window position k < filter_len - 1 -> frame of the clip)
   bool video_scored = false;
   int16_t video_hist[CVVDP_MAX_FILTER_LEN] = {};
+  // cvvdp_video_gradient_blocks_* (clips of several blocks): the padding map the clip's FIRST block was given (frame offset 0, float32
+  // frames handed in from frame 0 on), whether the block processed last came from float32 frames, and where the second walk stands
+  bool clip_hist_ok = false, last_block_f32 = false, blocks_begun = false;
+  int blocks_next = 0;                    // the frame the next cvvdp_video_gradient_block must start at
+  int blocks_key[7] = {};                 // ... and the clip cvvdp_video_gradient_blocks_begin saw: a block call after another clip was configured is refused
+  int16_t clip_hist[CVVDP_MAX_FILTER_LEN] = {};
 };
 
 namespace {
@@ -624,6 +630,7 @@ int cvvdp_configure(cvvdp_handle* h, const cvvdp_clip* clip) {
   h->last_items = 0; h->last_item0 = 0; h->last_q0 = 0;
   h->image_put = h->image_scored = false;
   h->video_scored = false;
+  h->clip_hist_ok = h->last_block_f32 = false;      // (blocks_begun stays: the second walk configures the same clip again)
   return CVVDP_OK;
 }
 
@@ -1203,6 +1210,162 @@ int cvvdp::grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t s
   return CVVDP_OK;
 }
 int cvvdp::grad_video_check_launch(cvvdp_handle* h) { return check_launch(h, "video_gradient"); }
+// cvvdp_video_gradient_blocks_begin / cvvdp_video_gradient_block (grad_blocks.hip) up to the launches.  The caller's scratch, in floats,
+// every part on a 256-byte granule, with items = block_frames * batch -- nothing in it grows with n_frames: the sums of the pooling
+// terms [batch] doubles; coef [items][4][L]; the slot variant's weights [4][fl - 1][fl]; three temporaries [4][items][P0]; per level d
+// [4][items][P_l] and (all but the baseband) ey [items][P_l]; the carry [fl][3][batch][P0]
+namespace {
+struct GradBlocksLayout { size_t sum, coef, padw, t[3], d[CVVDP_MAX_LEVELS], ey[CVVDP_MAX_LEVELS], carry, carry_floats, total; };
+bool grad_blocks_clip_ok(const cvvdp_handle* h) {
+  if (!h || !h->configured) return false;
+  const cvvdp_clip& c = h->c;
+  return c.is_video && c.channels == 3 && c.heatmap == CVVDP_HEATMAP_NONE && c.feature_size <= 0 && !c.defer_bands && h->fuse_levels == 0 &&
+         !h->pipeline && (int64_t)h->items_cap * 4 <= 65535;
+}
+GradBlocksLayout grad_blocks_layout(const cvvdp_handle* h) {
+  GradBlocksLayout g{};
+  const size_t B = (size_t)h->c.batch, items = (size_t)h->items_cap, fl = (size_t)h->c.filter_len;
+  size_t off = 0;
+  g.sum = off; off += align_up(2 * B);
+  g.coef = off; off += align_up(items * 4 * h->L);
+  g.padw = off; off += align_up(4 * (fl - 1) * fl);
+  for (int k = 0; k < 3; ++k) { g.t[k] = off; off += align_up(4 * items * (size_t)h->lv[0].P); }
+  for (int l = 0; l < h->L; ++l) {
+    g.d[l] = off; off += align_up(4 * items * (size_t)h->lv[l].P);
+    g.ey[l] = off; if (l + 1 < h->L) off += align_up(items * (size_t)h->lv[l].P);
+  }
+  g.carry_floats = fl * 3 * B * (size_t)h->lv[0].P;
+  g.carry = off; off += align_up(g.carry_floats);
+  g.total = off;
+  return g;
+}
+void grad_blocks_key(const cvvdp_handle* h, int (&key)[7]) {
+  const cvvdp_clip& c = h->c;
+  const int k[7] = {c.n_frames, c.batch, c.height, c.width, c.filter_len, c.block_frames, h->L};
+  for (int i = 0; i < 7; ++i) key[i] = k[i];
+}
+// what both entries check of the handle and the scratch, in the order of the other gradient entries
+int grad_blocks_checks(cvvdp_handle* h, const char* what, const void* scratch, size_t scratch_bytes, bool more_null, bool misaligned) {
+  if (!h) return CVVDP_E_STATE;
+  if (!scratch || more_null) return fail(h, CVVDP_E_ARG, "%s: null argument", what);
+  if (reinterpret_cast<uintptr_t>(scratch) % 16 || misaligned)
+    return fail(h, CVVDP_E_ARG, "%s: test and gradient must be 4-byte aligned, the scratch 16-byte aligned", what);
+  if (!h->configured) return fail(h, CVVDP_E_STATE, "%s: configure first", what);
+  const cvvdp_clip& c = h->c;
+  if (!c.is_video) return fail(h, CVVDP_E_STATE, "%s: configured for an image (cvvdp_image_gradient)", what);
+  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "%s: 1-channel content is out of scope", what);
+  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "%s: not with a heat map or features", what);
+  if (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG)
+    return fail(h, CVVDP_E_UNSUPPORTED, "%s: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)", what);
+  if (c.defer_bands) return fail(h, CVVDP_E_STATE, "%s: not for clips scored in pieces (defer_bands)", what);
+  if (h->fuse_levels != 0 || h->pipeline)
+    return fail(h, CVVDP_E_STATE, "%s: needs the unfused route (fuse_mode = 2), which keeps every pyramid level in the workspace", what);
+  if ((int64_t)h->items_cap * 4 > 65535)      // (4 planes per item in a grid's y)
+    return fail(h, CVVDP_E_UNSUPPORTED, "%s: blocks of %d frames x %d batch items are too many (4 planes per item, 65535 at most)", what, c.block_frames,
+                c.batch);
+  return CVVDP_OK;
+}
+}  // namespace
+size_t cvvdp::grad_blocks_scratch(const cvvdp_handle* h) { return grad_blocks_clip_ok(h) ? grad_blocks_layout(h).total * sizeof(float) : 0; }
+int cvvdp::grad_blocks_begin_prepare(cvvdp_handle* h, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan) {
+  const char* what = "video_gradient_blocks_begin";
+  if (int rc = grad_blocks_checks(h, what, scratch, scratch_bytes, false, false)) return rc;
+  const cvvdp_clip& c = h->c;
+  const GradBlocksLayout lay = grad_blocks_layout(h);
+  if (scratch_bytes < lay.total * sizeof(float)) return fail(h, CVVDP_E_ARG, "%s: scratch of %zu bytes, %zu needed", what, scratch_bytes, lay.total * sizeof(float));
+  h->blocks_begun = false;
+  const int B = c.batch, L = h->L, F = c.n_frames, fl = c.filter_len;
+  if (!h->ws || !h->clip_hist_ok || h->last_items < 1 || h->last_items % B != 0 || h->last_q0 + h->last_items / B != F)
+    return fail(h, CVVDP_E_STATE, "%s: valid after the cvvdp_process_block calls that scored all %d frames from float32 frames handed in from frame 0 on", what, F);
+  float* sc = static_cast<float*>(scratch);
+  plan = GradBlocksPlan{};
+  plan.L = L;
+  GradVideoPoolArgs& po = plan.pool.p;
+  po.q = h->ws + h->q_off; po.B = B; po.F = F; po.L = L;
+  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
+  for (int k = 0; k < 4; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
+  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.beta_t = h->p.beta_t; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp;
+  plan.pool.sum = reinterpret_cast<double*>(sc + lay.sum);
+  bool replicate = true;
+  for (int k = 0; k + 1 < fl; ++k) replicate = replicate && h->clip_hist[k] == 0;
+  plan.slots = !replicate || fl > CVVDP_GRAD_FIR_WL;
+  GradFirWeightArgs& fw = plan.fw;
+  fw.wt = sc + lay.padw; fw.F = F; fw.fl = fl;
+  for (int ch = 0; ch < 4; ++ch)
+    for (int k = 0; k < fl; ++k) fw.tflip[ch * CVVDP_MAX_FILTER_LEN + k] = c.taps[ch * CVVDP_MAX_FILTER_LEN + (fl - 1 - k)];
+  for (int k = 0; k + 1 < fl; ++k) fw.src[k] = h->clip_hist[k];
+  plan.fir.carry = sc + lay.carry; plan.carry_floats = lay.carry_floats;
+  return CVVDP_OK;
+}
+int cvvdp::grad_blocks_block_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes,
+                                     void* scratch, size_t scratch_bytes, GradBlocksPlan& plan) {
+  const char* what = "video_gradient_block";
+  if (int rc = grad_blocks_checks(h, what, scratch, scratch_bytes, !test || !st || !grad || !sg,
+                                  reinterpret_cast<uintptr_t>(test) % 4 || reinterpret_cast<uintptr_t>(grad) % 4))
+    return rc;
+  const cvvdp_clip& c = h->c;
+  const int B = c.batch, L = h->L, H = c.height, W = c.width, F = c.n_frames, fl = c.filter_len;
+  // the gradient's extent: the last element written is sum (size - 1) * stride over B, C, F, H, W of the whole clip
+  {
+    const int64_t dims[5] = {B, 3, F, H, W};
+    int64_t last = 0, term = 0;
+    bool bad = false;
+    for (int k = 0; k < 5 && !bad; ++k)
+      bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
+    if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
+      return fail(h, CVVDP_E_ARG, "%s: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d x %d samples at these strides", what, grad_bytes, B, F,
+                  H, W);
+  }
+  const GradBlocksLayout lay = grad_blocks_layout(h);
+  if (scratch_bytes < lay.total * sizeof(float)) return fail(h, CVVDP_E_ARG, "%s: scratch of %zu bytes, %zu needed", what, scratch_bytes, lay.total * sizeof(float));
+  int key[7];
+  grad_blocks_key(h, key);
+  if (!h->blocks_begun || std::memcmp(key, h->blocks_key, sizeof key) != 0)
+    return fail(h, CVVDP_E_STATE, "%s: call cvvdp_video_gradient_blocks_begin first, after all %d frames of this clip were scored", what, F);
+  if (!h->ws || h->last_items < 1 || h->last_item0 != 0 || h->last_items % B != 0 || h->last_q0 != h->blocks_next)
+    return fail(h, CVVDP_E_STATE, "%s: blocks out of order: the block processed last starts at frame %d, the gradient stands at frame %d", what, h->last_q0,
+                h->blocks_next);
+  if (!h->last_block_f32 || !h->clip_hist_ok) return fail(h, CVVDP_E_STATE, "%s: the block processed last was not scored from float32 frames", what);
+  const int items = h->last_items, n = items / B, q0 = h->last_q0;
+  float* sc = static_cast<float*>(scratch);
+  plan = GradBlocksPlan{};
+  plan.L = L; plan.items = items;
+  GradVideoPoolArgs& po = plan.pool.p;
+  po.q = h->ws + h->q_off; po.coef = sc + lay.coef; po.B = B; po.F = F; po.L = L;
+  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
+  for (int k = 0; k < 4; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
+  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.beta_t = h->p.beta_t; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp;
+  plan.pool.sum = reinterpret_cast<double*>(sc + lay.sum); plan.pool.q0 = q0; plan.pool.n = n;
+  fill_grad_chain<4>(h, items, sc, lay.t, lay.d, lay.ey, po.coef, plan.band, plan.base, plan.acc);
+  bool replicate = true;
+  for (int k = 0; k + 1 < fl; ++k) replicate = replicate && h->clip_hist[k] == 0;
+  plan.slots = !replicate || fl > CVVDP_GRAD_FIR_WL;
+  GradFirStreamArgs& s = plan.fir;
+  s.carry = sc + lay.carry; s.padw = sc + lay.padw; s.f0 = q0; s.n = n;
+  plan.carry_floats = lay.carry_floats;
+  GradFirAdjArgs& a = s.a;
+  a.G = sc + lay.d[0]; a.wt = nullptr;
+  a.test = static_cast<const float*>(test); a.tb = st[0]; a.tc = st[1]; a.tf = st[2]; a.th = st[3]; a.tw = st[4];
+  a.grad = grad; a.gb = sg[0]; a.gc = sg[1]; a.gf = sg[2]; a.gh = sg[3]; a.gw = sg[4];
+  a.H = H; a.W = W; a.B = B; a.F = F; a.fl = fl;
+  a.reg_wl = plan.slots ? 0 : (fl <= 9 ? 9 : (fl <= 17 ? 17 : CVVDP_GRAD_FIR_WL));
+  for (int ch = 0; ch < 4; ++ch)
+    for (int k = 0; k < fl; ++k) {
+      const float t = c.taps[ch * CVVDP_MAX_FILTER_LEN + (fl - 1 - k)];      // as the forward applies them (F.flip(0), cvvdp_metric.py:556)
+      s.tfull[ch * CVVDP_MAX_FILTER_LEN + k] = t;
+      if (k < CVVDP_GRAD_FIR_WL) a.tflip[ch * CVVDP_GRAD_FIR_WL + k] = t;
+    }
+  fill_display(h, a.dm);
+  return CVVDP_OK;
+}
+int cvvdp::grad_blocks_check_launch(cvvdp_handle* h, bool block) {
+  const int rc = check_launch(h, block ? "video_gradient_block" : "video_gradient_blocks_begin");
+  if (rc != CVVDP_OK) { h->blocks_begun = false; return rc; }
+  if (!block) { h->blocks_begun = true; h->blocks_next = 0; grad_blocks_key(h, h->blocks_key); return rc; }
+  h->blocks_next += h->last_items / h->c.batch;
+  if (h->blocks_next >= h->c.n_frames) h->blocks_begun = false;      // the clip's last block has flushed the carry
+  return rc;
+}
 // cvvdp_param_gradient (grad_param.hip) up to the launches.  The caller's scratch, every part on a 256-byte granule, sized for a full
 // block (items = block_frames * batch; 1 * batch for an image) of NC = 3 / 4 channels: coef [items][NC][L] floats; two temporaries
 // [NC][items][P0] floats; the slab [batch][block_frames * R][24] doubles, R = sum over the Laplacian levels of ceil(P_l / 2048), + 1
@@ -1526,6 +1689,16 @@ static int process_block_impl(cvvdp_handle* h, const void* t, const void* r, int
     h->video_hist[k] = (int16_t)hist_src[k];
   }
   h->video_scored = whole;
+  // ... and what cvvdp_video_gradient_block needs of it: float32 frames, and from the clip's first block the padding map
+  h->last_block_f32 = rc == CVVDP_OK && dtype == CVVDP_F32 && !yuv;
+  if (q_frame_offset == 0) {
+    bool first = h->last_block_f32 && raw_first == 0 && c.first_frame == 0;
+    for (int k = 0; k < fl_clip - 1 && first; ++k) {
+      first = hist_src[k] >= 0 && hist_src[k] < c.n_frames;
+      h->clip_hist[k] = (int16_t)hist_src[k];
+    }
+    h->clip_hist_ok = first;
+  }
   return rc;
 }
 
@@ -1550,6 +1723,7 @@ int cvvdp_process_block_filtered(cvvdp_handle* h, const void* t, const void* r, 
     launch_put_planes(a, s);
   }
   if (int e = check_launch(h, "put planes")) return e;
+  h->last_block_f32 = false;
   if (c.defer_bands) { h->filtered_frames = n_frames; h->filtered_q0 = q_frame_offset; return CVVDP_OK; }
   return run_pyramid_and_bands(h, n_frames, q_frame_offset, s);
 }

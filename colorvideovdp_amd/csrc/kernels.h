@@ -716,6 +716,42 @@ int grad_video_check_launch(cvvdp_handle* h);
 void launch_grad_chain4(int L, int items, const GradBandArgsT<4>* band, const GradBaseArgsT<4>& base, const GradAccumArgs* acc, hipStream_t s);
 void launch_video_gradient(const GradVideoPlan& p, hipStream_t s);
 
+// ---------------------------------------------------------------- gradient of the video JOD, block by block (grad_blocks.hip)
+// The same graph for a clip of any length, walked a second time block by block: cvvdp_video_gradient_blocks_begin adds up the pooling
+// terms of all frames, cvvdp_video_gradient_block runs the band chain over the block processed last and streams the FIR-plus-display
+// adjoint, whose open frames live in a carry of filter_len slots between the calls.
+struct GradBlocksPoolArgs {  // begin: sum[b] = the F pooling terms in ascending order; block: coef of frames [q0, q0 + n)
+  GradVideoPoolArgs p;      // p.coef: [n * B][4][L] of the block
+  double* sum;              // [B]
+  int32_t q0, n;
+};
+struct GradFirStreamArgs {
+  GradFirAdjArgs a;         // a.G: [4][n * B][H * W] of the block; a.F: frames of the CLIP; test and gradient of the whole clip
+  float* carry;             // [fl][3][B][H * W]
+  const float* padw;        // slot variant: [4][fl - 1][fl], weight of G_c[f] (f < fl - 1) in test frame j < fl
+  int32_t f0, n;            // the block's frames [f0, f0 + n)
+  float tfull[4 * CVVDP_MAX_FILTER_LEN];     // slot variant: [c][k] multiplies window position k
+};
+struct GradBlocksPlan {      // everything cvvdp_video_gradient_blocks_begin / _block launch, filled by core.cpp
+  int32_t L, items;
+  bool slots;               // the slot variant of the streamed adjoint (symmetric padding, or a filter beyond the register window)
+  GradBlocksPoolArgs pool;
+  GradBandArgsT<4> band[CVVDP_MAX_LEVELS];
+  GradBaseArgsT<4> base;
+  GradAccumArgs acc[CVVDP_MAX_LEVELS];
+  GradFirWeightArgs fw;     // fw.wt = padw
+  GradFirStreamArgs fir;
+  size_t carry_floats;
+};
+static_assert(sizeof(GradFirStreamArgs) <= 4096, "kernel arguments of the streamed FIR adjoint");
+size_t grad_blocks_scratch(const cvvdp_handle* h);
+int grad_blocks_begin_prepare(cvvdp_handle* h, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
+int grad_blocks_block_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
+                              size_t scratch_bytes, GradBlocksPlan& plan);
+int grad_blocks_check_launch(cvvdp_handle* h, bool block);      // ... and, after a block's launches, moves the handle on to the next block
+void launch_grad_blocks_begin(const GradBlocksPlan& p, hipStream_t s);
+void launch_grad_blocks_block(const GradBlocksPlan& p, hipStream_t s);
+
 // ---------------------------------------------------------------- gradient of the JOD in the model's parameters (grad_param.hip, grad_param_dev.h)
 // d JOD[b] / d (mask_p, mask_c, mask_q, xcm_weights, d_max, sensitivity_correction) of the block processed last, added to acc [B][24].
 // Per Laplacian level: k_grad_min and the forward blur of the chain above, then one per-pixel kernel whose blocks each leave a row of 24

@@ -268,8 +268,8 @@ class _JodLoss(torch.autograd.Function):
     """10 - JOD with the gradient of cvvdp.predict_with_gradient (cvvdp.differentiable_loss)."""
 
     @staticmethod
-    def forward(ctx, test, reference, metric, dim_order, frames_per_second):
-        jod, grad = metric.predict_with_gradient(test, reference, dim_order, frames_per_second)
+    def forward(ctx, test, reference, metric, dim_order, frames_per_second, block_frames=None):
+        jod, grad = metric.predict_with_gradient(test, reference, dim_order, frames_per_second, block_frames=block_frames)
         ctx.save_for_backward(grad)
         ctx.batch_shape = [n if ch == "B" else 1 for ch, n in zip(dim_order.upper(), grad.shape)]
         return 10.0 - jod
@@ -278,7 +278,7 @@ class _JodLoss(torch.autograd.Function):
     def backward(ctx, upstream):
         grad, = ctx.saved_tensors
         up = upstream if upstream.dim() == 0 else upstream.reshape(ctx.batch_shape)      # one factor per batch item
-        return -grad * up, None, None, None, None
+        return -grad * up, None, None, None, None, None
 
 
 _CSF_TABLES = {}
@@ -624,8 +624,11 @@ class cvvdp(vq_metric):
         Q_jod, _ = self.predict(test_cont, reference_cont, dim_order=dim_order, frames_per_second=frames_per_second)
         return 10.0 - Q_jod
 
-    def _gradient_inputs(self, test, reference, dim_order, frames_per_second=0):
+    def _gradient_inputs(self, test, reference, dim_order, frames_per_second=0, block_frames=None):
         """What predict_with_gradient refuses, checked before anything touches the device; returns the BCFHW views."""
+        if block_frames is not None and block_frames != "auto":
+            if isinstance(block_frames, bool) or not isinstance(block_frames, (int, np.integer)) or block_frames < 1:
+                raise vq_exception(f'predict_with_gradient: block_frames must be None, "auto" or an integer >= 1, not {block_frames!r}')
         if not torch.is_tensor(test) or not torch.is_tensor(reference):
             raise vq_exception("predict_with_gradient: test and reference must be torch tensors")
         if test.dtype != torch.float32 or reference.dtype != torch.float32:
@@ -646,7 +649,12 @@ class cvvdp(vq_metric):
             fl = hs.temporal_filters(frames_per_second, self.parameters["beta_tf"], self.parameters["sigma_tf"]).shape[1]
             if fl > _capi.MAX_FILTER_LEN:
                 raise vq_exception(f"frame rates above {(_capi.MAX_FILTER_LEN - 1) * 4} fps are not supported")
-            if t.shape[2] + fl - 1 > _capi.MAX_WINDOW:
+            if block_frames is not None:
+                nb = t.shape[2] if block_frames == "auto" else min(int(block_frames), t.shape[2])
+                if block_frames != "auto" and nb + fl - 1 > _capi.MAX_WINDOW:
+                    raise vq_exception(f"predict_with_gradient: block_frames = {nb} with a filter of {fl} taps exceeds the window limit of a temporal block, "
+                                       f"CVVDP_MAX_WINDOW = {_capi.MAX_WINDOW} (block_frames + filter_len - 1)")
+            elif t.shape[2] + fl - 1 > _capi.MAX_WINDOW:
                 raise vq_exception(f"predict_with_gradient: the video must be scored as one temporal block, and {t.shape[2]} frames with a filter of {fl} taps "
                                    f"exceed the window limit CVVDP_MAX_WINDOW = {_capi.MAX_WINDOW} (n_frames + filter_len - 1)")
         if t.shape[1] != 3 or r.shape[1] != 3:
@@ -662,7 +670,7 @@ class cvvdp(vq_metric):
             raise vq_exception(f"predict_with_gradient: test and reference must be tensors on {self.device}")
         return t, r
 
-    def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0):
+    def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None):
         """(jod, grad) of an image or of a short clip: `jod` as predict() returns it, `grad` = d jod / d test, float32 on the device, with
         the shape of `test` in the caller's dim_order; for a batch, grad[b] is the gradient of jod[b] (items do not interact).  float32
         tensors on the metric's device, three channels; sRGB, numeric-gamma and linear displays.  1-channel content, other dtypes, heat
@@ -675,10 +683,21 @@ class cvvdp(vq_metric):
         fuse_mode = 2 and block_frames = n_frames are set for this call and restored, so the JOD is that of predict() with those two
         settings, and equal to the default predict() to the rounding between the routes.  A clip whose window n_frames + filter_len - 1
         exceeds CVVDP_MAX_WINDOW (256), or whose workspace and scratch (about 75 bytes per pixel, frame and batch item on top of the
-        forward's 43) cannot be allocated, is refused.  Out of scope: clips longer than one block (a two-pass recompute), file sources,
-        .yuv, --temp-resample, frame sharding."""
-        t, r = self._gradient_inputs(test, reference, dim_order, frames_per_second)
+        forward's 43) cannot be allocated, is refused.
+        Clips of any length: block_frames = N (an integer >= 1) scores and differentiates the clip in temporal blocks of N frames, the
+        last one shorter (cvvdp_video_gradient_block, csrc/grad_blocks.hip): fuse_mode = 2 and block_frames = N are set for the call and
+        restored, the JOD is that of predict() with those two settings, bit for bit, and the gradient is the same bits for every N
+        (N >= n_frames included).  Against block_frames = None, where that is accepted, the JOD is the same bits and the gradient is
+        the same bits under symmetric padding and beyond 33 taps; under replicate padding up to 33 taps the two differ in how one
+        multiply-add per tap is fused (1e-7 of the largest sample).  The clip is walked twice (pooling over frames couples the frames); a clip
+        of one block once.  Workspace and scratch then grow with N, not with the clip: about 118 bytes per pixel and batch item x N, plus
+        12 bytes x filter_len for what a block border cuts; only `grad` has the clip's size.  N + filter_len - 1 must not exceed
+        CVVDP_MAX_WINDOW.  block_frames = "auto" takes the largest N the window limit and the free memory allow.  Images ignore it.
+        Out of scope: file sources, .yuv, --temp-resample, frame sharding."""
+        t, r = self._gradient_inputs(test, reference, dim_order, frames_per_second, block_frames)
         if t.shape[2] > 1:
+            if block_frames is not None:
+                return self._predict_video_with_gradient_blocks(test, t, r, dim_order, frames_per_second, block_frames)
             return self._predict_video_with_gradient(test, t, r, dim_order, frames_per_second)
         vs = video_source_array(t, r, 0, dim_order="BCFHW", display_photometry=self.display_photometry)
         Q, _, _ = self._score_range(vs, 0, 1)
@@ -731,14 +750,65 @@ class cvvdp(vq_metric):
             del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
         return jod.squeeze(), grad
 
-    def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0):
+    def _predict_video_with_gradient_blocks(self, test, t, r, dim_order, frames_per_second, block_frames):
+        """predict_with_gradient for a clip in temporal blocks: t, r are the BCFHW views on the device.  Pass 1 scores all blocks; the
+        pooling terms of all frames are added on the device; pass 2 runs the same blocks again, the backward of a block after each."""
+        if self._shard is not None:
+            raise vq_exception("predict_with_gradient: not available with frame sharding")
+        lib = _capi.lib()
+        n_frames = int(t.shape[2])
+        saved = (self.fuse_mode, self.block_frames)
+        auto = block_frames == "auto"
+        self.fuse_mode, self.block_frames = 2, (None if auto else min(int(block_frames), n_frames))
+        self._pixel_grad_plan = True         # (_pick_block_frames counts the backward's scratch when it sizes the blocks itself)
+        scratch = None
+        try:
+            vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
+            try:
+                Q, _, _ = self._score_range(vs, 0, n_frames)                   # pass 1: the normal block loop
+                self.block_frames = int(self.last_block_frames)                # (pass 2 walks the same blocks, whatever is free by then)
+                need = int(lib.cvvdp_video_gradient_blocks_scratch_bytes(self._handle))
+                scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            except torch.cuda.OutOfMemoryError:
+                ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_blocks_scratch_bytes(self._handle))
+                self._ws = None
+                raise vq_exception(f"predict_with_gradient: blocks of {self.last_block_frames} frames need a workspace of {ws} bytes and a scratch of "
+                                   f"{sc} bytes, which cannot be allocated on this device") from None
+            jod = self.do_pooling_and_jods(Q)
+            grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
+            gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
+            assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
+            st = (ctypes.c_int64 * 5)(*t.stride())
+            sg = (ctypes.c_int64 * 5)(*gv.stride())
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = lib.cvvdp_video_gradient_blocks_begin(self._handle, scratch.data_ptr(), scratch.numel(), stream)
+            _capi.check(self._handle, rc, "cvvdp_video_gradient_blocks_begin")
+
+            def after_block(stream):
+                rc = lib.cvvdp_video_gradient_block(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(),
+                                                    scratch.numel(), stream)
+                _capi.check(self._handle, rc, "cvvdp_video_gradient_block")
+
+            if n_frames <= int(self.last_block_frames):
+                after_block(stream)                                             # one block: its pyramid is still in the workspace
+            else:
+                self._block_hook = after_block                                  # pass 2: the same blocks again, the entry after each
+                self._score_range(vs, 0, n_frames)
+        finally:
+            self.fuse_mode, self.block_frames = saved
+            self._pixel_grad_plan, self._block_hook = False, None
+            del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
+        return jod.squeeze(), grad
+
+    def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None):
         """10 - JOD of an image or a short clip as a tensor attached to autograd (the reference's loss(): examples/ex_image_reconstruction.py
         runs with this method's name in place of `loss`).  backward() multiplies the gradient predict_with_gradient() stored by the
         upstream gradient, one factor per batch item; the reference receives None, and a reference that requires a gradient is refused.
-        Clips: see predict_with_gradient."""
+        Clips: see predict_with_gradient; block_frames (None, an integer or "auto") is handed on to it, so that a clip of any length can
+        serve as a loss."""
         if torch.is_tensor(reference) and reference.requires_grad:
             raise vq_exception("differentiable_loss: a gradient for the reference is out of scope")
-        return _JodLoss.apply(test, reference, self, dim_order, frames_per_second)
+        return _JodLoss.apply(test, reference, self, dim_order, frames_per_second, block_frames)
 
     # ------------------------------------------------------------------ gradient in the model's parameters (calibration)
     @staticmethod
@@ -1007,6 +1077,10 @@ class cvvdp(vq_metric):
             if getattr(self, "_param_grad_plan", False):
                 per_frame += pix * batch * (2 * nch * 4 + 1)      # cvvdp_param_gradient's scratch: two temporaries of nch planes and the slab of row sums
             fixed = pix * batch * 24 * (fl - 1)
+            if getattr(self, "_pixel_grad_plan", False):
+                # cvvdp_video_gradient_block's scratch: three temporaries of 4 planes, 4 + 1 planes per pyramid level; the carry of fl slots
+                per_frame += pix * batch * (3 * 4 * 4 + 5 * 4 * 1.34)
+                fixed += pix * batch * 12 * fl
             nb = int((budget - fixed) // per_frame)
             # heat maps leave the GPU over PCIe (2-6 B/pixel): 16-frame blocks let the copy of a block overlap the
             # kernels of the next one (4K supra-threshold, 64 frames: 111 ms as one block, 81 ms in blocks of 16)
@@ -1155,7 +1229,7 @@ class cvvdp(vq_metric):
         height, width, is_image, prefiltered = rt.height, rt.width, rt.is_image, rt.prefiltered
         key = (height, width, rt.n_total, first, count, rt.B, rt.C, is_image, None if is_image else float(vs.get_frames_per_second()), self.heatmap,
                bool(self.debug_dump or self.dump_channels is not None), int(self.fuse_mode), int(self.band_layout), self.score_frames, self._sink_on_device, self.block_frames, self.gpu_mem, float(self.pix_per_deg), self._cfg_version, prefiltered, getattr(self, "_feature_out", None) is not None,
-               self._host_resident(vs), bool(getattr(self, "_param_grad_plan", False)))
+               self._host_resident(vs), bool(getattr(self, "_param_grad_plan", False)), bool(getattr(self, "_pixel_grad_plan", False)))
         cached = getattr(self, "_clip_cache", None)
         if cached is not None and cached[0] == key:
             clip, fl, F = cached[1], cached[2], cached[3]

@@ -507,6 +507,41 @@ size_t cvvdp_video_gradient_scratch_bytes(const cvvdp_handle* h);
 int cvvdp_video_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                          size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* The same gradient for a clip of ANY length, block by block.  Valid on a video clip of three channels configured without heat map,
+ * features and defer_bands on the unfused route, with any block_frames (block_frames + filter_len - 1 <= CVVDP_MAX_WINDOW as for every
+ * clip).  Pooling over frames couples the frames, so the clip is walked twice:
+ *   1. cvvdp_process_block for every block, in order, from fp32 frames (dtype CVVDP_F32) handed in from frame 0 on: Q_per_ch of all
+ *      frames.  The handle remembers the padding map of the first block (frame offset 0, raw_first 0, every hist_src entry a frame
+ *      of the clip).
+ *   2. cvvdp_video_gradient_blocks_begin: the pooling terms of all frames, added in float64 in ascending frame order (for clips that
+ *      fit one block: the coefficients of cvvdp_video_gradient, bit for bit); zeroes the carry.
+ *   3. the same cvvdp_process_block calls again, each followed by cvvdp_video_gradient_block, which runs the band chain over the
+ *      frames of the block processed last and hands out every gradient frame nothing can reach any more; the call after the clip's last
+ *      block hands out the rest.  A clip of one block needs no second walk: begin and one block call after the only
+ *      cvvdp_process_block.
+ *   dev_test, dev_grad   the WHOLE clip (B x 3 x n_frames x H x W), as for cvvdp_video_gradient; the same pointers in every call
+ *   dev_scratch    cvvdp_video_gradient_blocks_scratch_bytes(h) bytes, 16-byte aligned, the same buffer from begin to the last block
+ *                  call (0 where the clip is not one the entries exist for).  It does not depend on n_frames.  In floats, every part
+ *                  rounded up to 64, with items = block_frames * batch, fl = filter_len and P_l the pixels of level l: 2 * batch (the
+ *                  sums); coef items * 4 * L; the padding weights 4 * (fl - 1) * fl; three temporaries of 4 * items * P_0; per level
+ *                  4 * items * P_l, and items * P_l more on all but the last; the carry fl * 3 * batch * P_0.  Per pixel and batch
+ *                  item about 75 bytes x block_frames + 12 bytes x filter_len
+ * The adjoint of the temporal FIR, fused with the display model's, is streamed: a frame's contributions arrive from up to
+ * filter_len - 1 later frames, and what a block border cuts waits in the carry -- under replicate padding and up to 33 taps the open
+ * window positions and the sum of the padding positions, otherwise the open frames' sums with the folded weights of the gather variant.
+ * Every float is added in the order of the one-block walk and every rounding is spelled out, so the gradient does not depend on where
+ * the clip is cut, bit for bit; it equals cvvdp_video_gradient's where that entry takes its gather variant, and differs from its
+ * register variant (replicate padding, up to 33 taps) only in how the compiler fuses one multiply-add per tap there.  Per-thread serial walks and gathers without atomics.  Nothing
+ * synchronises.  Null or misaligned pointers, negative strides, a short gradient buffer or scratch give CVVDP_E_ARG; 1 channel, heat
+ * map, features, PQ / HLG, or more than 65535 / 4 block_frames x batch items CVVDP_E_UNSUPPORTED; no configured video clip,
+ * defer_bands, a fused route, begin before the whole clip was scored, a block call before begin, blocks out of order, or a block
+ * that was not scored from float32 frames CVVDP_E_STATE -- all before any launch.  Added; nothing else changed, so CVVDP_ABI_VERSION
+ * stays 14. */
+size_t cvvdp_video_gradient_blocks_scratch_bytes(const cvvdp_handle* h);
+int cvvdp_video_gradient_blocks_begin(cvvdp_handle* h, void* dev_scratch, size_t scratch_bytes, void* stream);
+int cvvdp_video_gradient_block(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
+                               size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Gradient of the JOD in the model's PARAMETERS, for calibration: dev_acc[b][j] += d JOD[b] / d parameter j over the frames of the block
  * processed last, with the parameters as the parameter file stores them (mask_c and d_max as exponents of 10, xcm_weights as exponents
  * of 2, sensitivity_correction in dB).  Slots j: 0 mask_p, 1 mask_c, 2..5 mask_q[0..3], 6..21 xcm_weights[0..15], 22 d_max,
