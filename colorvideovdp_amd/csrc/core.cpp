@@ -1001,35 +1001,137 @@ int cvvdp::mt_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_
   return CVVDP_OK;
 }
 int cvvdp::mt_head_check_launch(cvvdp_handle* h) { return check_launch(h, "ml_transformer_head"); }
-// cvvdp_image_gradient (grad.hip) up to the launches.  The caller's scratch, in floats, every part on a 256-byte granule:
-// coef [B][3][L]; three temporaries [3][B][P0]; per level d [3][B][P_l] and (all but the baseband) ey [B][P_l]
+// ---------------------------------------------------------------- the gradient routes up to the launches
+// cvvdp_image_gradient (grad.hip), cvvdp_video_gradient (grad_video.hip), cvvdp_video_gradient_blocks_begin / cvvdp_video_gradient_block
+// (grad_blocks.hip) and cvvdp_param_gradient (grad_param.hip) share one scratch layout, one ordered refusal list and one band chain.
 namespace {
-struct GradLayout { size_t coef, t[3], d[CVVDP_MAX_LEVELS], ey[CVVDP_MAX_LEVELS], total; };
-bool grad_clip_ok(const cvvdp_handle* h) { return h && h->configured && !h->c.is_video && h->c.channels == 3; }
-GradLayout grad_layout(const cvvdp_handle* h) {
+enum GradRoute { kGradImage, kGradVideo, kGradBlocksBegin, kGradBlocksBlock, kGradParam };
+const char* const kGradName[] = {"image_gradient", "video_gradient", "video_gradient_blocks_begin", "video_gradient_block", "param_gradient"};
+// What a route keeps in the caller's scratch: the band chain's NC channels over `items` items with n_t temporaries and, per level, its
+// outputs or none; the extras in floats (0: none).  Call it for a configured handle only.
+struct GradShape { int NC; size_t items; int n_t; bool outputs; size_t sum, wt, carry; bool slab; };
+GradShape grad_shape(const cvvdp_handle* h, GradRoute r) {
+  const cvvdp_clip& c = h->c;
+  const size_t B = (size_t)c.batch, F = (size_t)c.n_frames, fl = (size_t)c.filter_len, block = (size_t)h->items_cap;
+  switch (r) {
+    case kGradImage: return {3, B, 3, true, 0, 0, 0, false};
+    case kGradVideo: return {4, F * B, 3, true, 0, 4 * F * F, 0, false};                   // wt: the gather variant's table [4][F][F]
+    case kGradParam: return {h->nch, block, 2, false, 0, 0, 0, true};                      // a full block (an image: 1 * batch)
+    default:         return {4, block, 3, true, 2 * B, 4 * (fl - 1) * fl, fl * 3 * B * (size_t)h->lv[0].P, false};
+  }     // (blocks: nothing grows with n_frames.  sum: [batch] doubles; wt: the slot variant's weights; carry: [fl][3][batch][P0])
+}
+// The scratch, in float offsets, every region on a 256-byte granule and in this order: sum; coef [items][NC][L]; wt; the temporaries
+// [NC][items][P0]; per level d [NC][items][P_l] and (all but the baseband) ey [items][P_l]; carry; the slab [items][R][24] doubles,
+// R = sum over the Laplacian levels of ceil(P_l / 2048), + 1.  A region the route does not have takes no room.
+struct GradLayout {
+  size_t sum, coef, wt, t[3], d[CVVDP_MAX_LEVELS], ey[CVVDP_MAX_LEVELS], carry, carry_floats, slab, total;
+  bool outputs;
+  int nblk[CVVDP_MAX_LEVELS], row_off[CVVDP_MAX_LEVELS], rows_frame;      // slab: blocks of a level, its first row, rows per frame
+};
+GradLayout grad_layout(const cvvdp_handle* h, GradRoute r) {
+  const GradShape s = grad_shape(h, r);
   GradLayout g{};
-  const size_t B = (size_t)h->c.batch;
+  const size_t NC = (size_t)s.NC;
   size_t off = 0;
-  g.coef = off; off += align_up(B * 3 * h->L);
-  for (int k = 0; k < 3; ++k) { g.t[k] = off; off += align_up(3 * B * (size_t)h->lv[0].P); }
-  for (int l = 0; l < h->L; ++l) {
-    g.d[l] = off; off += align_up(3 * B * (size_t)h->lv[l].P);
-    g.ey[l] = off; if (l + 1 < h->L) off += align_up(B * (size_t)h->lv[l].P);
+  auto take = [&off](size_t n_floats) { const size_t at = off; off += align_up(n_floats); return at; };
+  g.sum = take(s.sum);
+  g.coef = take(s.items * NC * h->L);
+  g.wt = take(s.wt);
+  for (int k = 0; k < 3; ++k) g.t[k] = k < s.n_t ? take(NC * s.items * (size_t)h->lv[0].P) : g.t[0];      // (a missing one: never written, any address)
+  g.outputs = s.outputs;
+  for (int l = 0; l < h->L && s.outputs; ++l) {
+    g.d[l] = take(NC * s.items * (size_t)h->lv[l].P);
+    g.ey[l] = l + 1 < h->L ? take(s.items * (size_t)h->lv[l].P) : off;
+  }
+  g.carry_floats = s.carry; g.carry = take(s.carry);
+  if (s.slab) {
+    for (int l = 0; l < h->L; ++l) {
+      g.nblk[l] = l + 1 < h->L ? (int)((h->lv[l].P + CVVDP_PARAM_BLOCK_PX - 1) / CVVDP_PARAM_BLOCK_PX) : 1;
+      g.row_off[l] = g.rows_frame; g.rows_frame += g.nblk[l];
+    }
+    g.slab = take(s.items * (size_t)g.rows_frame * CVVDP_PARAM_GRAD_COUNT * 2);      // (doubles: two floats each)
   }
   g.total = off;
   return g;
 }
+// The refusal list, in the order every route checks it.  say = h: the prepare's answer, with the message.  say = null: the silent
+// answer of *_scratch_bytes (the handle is const there and the error text is not theirs to write), which looks at the configured clip
+// alone: not at the call's pointers, not at the display -- and for an image at no more than the two checks its first version made.
+int grad_checks(const cvvdp_handle* h, cvvdp_handle* say, GradRoute r, bool null_arg, bool misaligned) {
+  if (!h) return CVVDP_E_STATE;
+  const char* what = kGradName[r];
+  auto no = [&](int code, const char* fmt, auto... a) { return say ? fail(say, code, fmt, what, a...) : code; };
+  if (null_arg) return no(CVVDP_E_ARG, "%s: null argument");
+  if (misaligned)
+    return no(CVVDP_E_ARG, r == kGradParam ? "%s: dq must be 4-byte aligned, acc 8-byte aligned, the scratch 16-byte aligned"
+                                           : "%s: test and gradient must be 4-byte aligned, the scratch 16-byte aligned");
+  if (!h->configured) return no(CVVDP_E_STATE, "%s: configure first");
+  const cvvdp_clip& c = h->c;
+  if (r == kGradImage && c.is_video) return no(CVVDP_E_STATE, "%s: configured for video; the gradient exists for images only");
+  if (r != kGradImage && r != kGradParam && !c.is_video) return no(CVVDP_E_STATE, "%s: configured for an image (cvvdp_image_gradient)");
+  if (c.channels != 3) return no(CVVDP_E_UNSUPPORTED, "%s: 1-channel content is out of scope");
+  if (r == kGradImage && !say) return CVVDP_OK;
+  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return no(CVVDP_E_UNSUPPORTED, "%s: not with a heat map or features");
+  if (say && r != kGradParam && (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG))
+    return no(CVVDP_E_UNSUPPORTED, "%s: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)");
+  if (r != kGradImage) {
+    if (c.defer_bands) return no(CVVDP_E_STATE, "%s: not for clips scored in pieces (defer_bands)");
+    if (r == kGradVideo && c.block_frames < c.n_frames)
+      return no(CVVDP_E_STATE, "%s: the clip must be one temporal block (block_frames %d < n_frames %d)", c.block_frames, c.n_frames);
+    if (c.is_video && (h->fuse_levels != 0 || h->pipeline))
+      return no(CVVDP_E_STATE, "%s: needs the unfused route (fuse_mode = 2), which keeps every pyramid level in the workspace");
+  }
+  const GradShape s = grad_shape(h, r);
+  if (s.items * (size_t)s.NC > 65535) {      // (NC planes per item in a grid's y)
+    if (r == kGradImage) return no(CVVDP_E_UNSUPPORTED, "%s: batch of %d too large", c.batch);
+    return no(CVVDP_E_UNSUPPORTED, "%s: %s%d frames x %d batch items are too many (%d planes per item, 65535 at most)",
+              r == kGradVideo || r == kGradParam ? "" : "blocks of ", r == kGradVideo ? c.n_frames : (c.is_video ? c.block_frames : 1), c.batch, s.NC);
+  }
+  return CVVDP_OK;
+}
+size_t grad_scratch_bytes(const cvvdp_handle* h, GradRoute r) {
+  return grad_checks(h, nullptr, r, false, false) == CVVDP_OK ? grad_layout(h, r).total * sizeof(float) : 0;
+}
+// What every prepare does before it looks at the call order: the refusal list; with strides, the gradient's extent (the last element
+// written is sum (size - 1) * stride over B, C, F, H, W of the whole clip; an image has no F); the layout and the scratch's size.
+int grad_front(cvvdp_handle* h, GradRoute r, bool null_arg, bool misaligned, const int64_t* st, const int64_t* sg, size_t grad_bytes, size_t scratch_bytes,
+               GradLayout& lay) {
+  if (int rc = grad_checks(h, h, r, null_arg, misaligned)) return rc;
+  const char* what = kGradName[r];
+  const cvvdp_clip& c = h->c;
+  if (sg) {
+    const int64_t dims[5] = {c.batch, 3, c.n_frames, c.height, c.width};
+    int64_t last = 0, term = 0;
+    bool bad = false;
+    for (int k = 0; k < 5 && !bad; ++k) {
+      if (k == 2 && r == kGradImage) continue;
+      bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
+    }
+    if ((bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float))) && r == kGradImage)
+      return fail(h, CVVDP_E_ARG, "%s: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d samples at these strides", what, grad_bytes, c.batch,
+                  c.height, c.width);
+    if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
+      return fail(h, CVVDP_E_ARG, "%s: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d x %d samples at these strides", what, grad_bytes,
+                  c.batch, c.n_frames, c.height, c.width);
+  }
+  lay = grad_layout(h, r);
+  if (scratch_bytes < lay.total * sizeof(float)) return fail(h, CVVDP_E_ARG, "%s: scratch of %zu bytes, %zu needed", what, scratch_bytes, lay.total * sizeof(float));
+  return CVVDP_OK;
+}
+bool misaligned4(const void* a, const void* b) { return reinterpret_cast<uintptr_t>(a) % 4 || reinterpret_cast<uintptr_t>(b) % 4; }
+bool misaligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; }
 // the band chain of a gradient plan (levels, baseband, pyramid adjoints) for NC channels over `items` items: forward planes from the
-// workspace, everything else at the given float offsets of the caller's scratch
+// workspace, everything else at the layout's offsets of the caller's scratch.  A layout without per-level outputs (the parameter
+// gradient, whose own kernels take the place of those that write them) leaves d and ey at the scratch's start and the adjoints empty.
 template <int NC>
-void fill_grad_chain(const cvvdp_handle* h, int items, float* sc, const size_t (&t)[3], const size_t* d, const size_t* ey, const float* coef,
-                     GradBandArgsT<NC>* band, GradBaseArgsT<NC>& base, GradAccumArgs* acc) {
+void fill_grad_chain(const cvvdp_handle* h, int items, float* sc, const GradLayout& lay, const float* coef, GradChain<NC>& ch) {
   const int L = h->L;
   const float K[5] = {kGaussK0, 0.25f, 0.4f, 0.25f, kGaussK0};
+  ch.L = L; ch.items = items;
   for (int l = 0; l + 1 < L; ++l) {
     const Level& lv = h->lv[l];
     const Level& lc = h->lv[l + 1];
-    GradBandArgsT<NC>& a = band[l];
+    GradBandArgsT<NC>& a = ch.band[l];
     a.g = gbase(h, l, 0); a.gps = (int64_t)level_cap(h, l) * lv.P;
     a.gc = gbase(h, l + 1, 0); a.gcps = (int64_t)h->items_cap_s * lc.P;
     a.H = lv.H; a.W = lv.W; a.Hc = lc.H; a.Wc = lc.W; a.B = items; a.blur = lv.blur; a.level = l; a.L = L;
@@ -1044,280 +1146,147 @@ void fill_grad_chain(const cvvdp_handle* h, int items, float* sc, const size_t (
     a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
     for (int k = 0; k < 13; ++k) a.taps[k] = h->p.blur_taps[k];
     a.coef = coef;
-    a.t0 = sc + t[0]; a.t1 = sc + t[1]; a.t2 = sc + t[2];
-    a.d = sc + d[l]; a.ey = sc + ey[l];
+    a.t0 = sc + lay.t[0]; a.t1 = sc + lay.t[1]; a.t2 = sc + lay.t[2];
+    a.d = sc + lay.d[l]; a.ey = sc + lay.ey[l];
   }
   {
     const Level& lv = h->lv[L - 1];
-    GradBaseArgsT<NC>& b = base;
+    GradBaseArgsT<NC>& b = ch.base;
     b.g = gbase(h, L - 1, 0); b.gps = (int64_t)level_cap(h, L - 1) * lv.P;
     b.H = lv.H; b.W = lv.W; b.B = items; b.level = L - 1; b.L = L;
     std::memcpy(b.lut, h->c.csf_rows + (size_t)(L - 1) * 4 * CVVDP_CSF_NODES, sizeof b.lut);
     b.logL_first = h->p.csf_logL_first; b.logL_last = h->p.csf_logL_last; b.sens_mul = h->p.sens_mul;
-    b.coef = coef; b.d = sc + d[L - 1];
+    b.coef = coef; b.d = sc + lay.d[L - 1];
   }
-  for (int l = 0; l < L; ++l) {
-    GradAccumArgs& a = acc[l];
-    a.d = sc + d[l]; a.H = h->lv[l].H; a.W = h->lv[l].W; a.B = items;
-    if (l > 0) { a.d_f = sc + d[l - 1]; a.ey_f = sc + ey[l - 1]; a.Hf = h->lv[l - 1].H; a.Wf = h->lv[l - 1].W; }
-    if (l + 1 < L) { a.tot_c = sc + d[l + 1]; a.Hc = h->lv[l + 1].H; a.Wc = h->lv[l + 1].W; }
+  for (int l = 0; l < L && lay.outputs; ++l) {
+    GradAccumArgs& a = ch.acc[l];
+    a.d = sc + lay.d[l]; a.H = h->lv[l].H; a.W = h->lv[l].W; a.B = items;
+    if (l > 0) { a.d_f = sc + lay.d[l - 1]; a.ey_f = sc + lay.ey[l - 1]; a.Hf = h->lv[l - 1].H; a.Wf = h->lv[l - 1].W; }
+    if (l + 1 < L) { a.tot_c = sc + lay.d[l + 1]; a.Hc = h->lv[l + 1].H; a.Wc = h->lv[l + 1].W; }
     a.kx[0] = K[0] * 2.0f; a.kx[1] = K[2] * 2.0f; a.kx[2] = K[1] * 2.0f;
     for (int k = 0; k < 5; ++k) a.K[k] = K[k];
   }
 }
-}  // namespace
-size_t cvvdp::grad_scratch(const cvvdp_handle* h) { return grad_clip_ok(h) ? grad_layout(h).total * sizeof(float) : 0; }
-int cvvdp::grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
-                        size_t scratch_bytes, GradPlan& plan) {
-  if (!h) return CVVDP_E_STATE;
-  if (!test || !st || !grad || !sg || !scratch) return fail(h, CVVDP_E_ARG, "image_gradient: null argument");
-  if (reinterpret_cast<uintptr_t>(test) % 4 || reinterpret_cast<uintptr_t>(grad) % 4 || reinterpret_cast<uintptr_t>(scratch) % 16)
-    return fail(h, CVVDP_E_ARG, "image_gradient: test and gradient must be 4-byte aligned, the scratch 16-byte aligned");
-  if (!h->configured) return fail(h, CVVDP_E_STATE, "image_gradient: configure first");
-  const cvvdp_clip& c = h->c;
-  if (c.is_video) return fail(h, CVVDP_E_STATE, "image_gradient: configured for video; the gradient exists for images only");
-  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: 1-channel content is out of scope");
-  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: not with a heat map or features");
-  if (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG)
-    return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)");
-  if (c.batch > 21845) return fail(h, CVVDP_E_UNSUPPORTED, "image_gradient: batch of %d too large", c.batch);   // (3 planes per item in a grid's y)
-  const int B = c.batch, L = h->L, H = c.height, W = c.width;
-  // the gradient's extent: the last element written is sum (size - 1) * stride over B, C, H, W
-  {
-    const int64_t dims[5] = {B, 3, 1, H, W};
-    int64_t last = 0, term = 0;
-    bool bad = false;
-    for (int k = 0; k < 5 && !bad; ++k) {
-      if (k == 2) continue;
-      bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
-    }
-    if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
-      return fail(h, CVVDP_E_ARG, "image_gradient: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d samples at these strides", grad_bytes, B, H, W);
-  }
-  const GradLayout lay = grad_layout(h);
-  if (scratch_bytes < lay.total * sizeof(float))
-    return fail(h, CVVDP_E_ARG, "image_gradient: scratch of %zu bytes, %zu needed", scratch_bytes, lay.total * sizeof(float));
-  if (!h->ws || !h->image_scored) return fail(h, CVVDP_E_STATE, "image_gradient: valid after cvvdp_put_image and cvvdp_process_image");
-  float* sc = static_cast<float*>(scratch);
-  plan = GradPlan{};
-  plan.L = L;
-  GradPoolArgs& po = plan.pool;
-  po.q = h->ws + h->q_off; po.coef = sc + lay.coef; po.B = B; po.L = L;
-  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
-  for (int k = 0; k < 3; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
-  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp; po.image_int = h->p.image_int;
-  fill_grad_chain<3>(h, B, sc, lay.t, lay.d, lay.ey, po.coef, plan.band, plan.base, plan.acc);
-  GradDisplayArgs& d = plan.dsp;
-  d.tot = sc + lay.d[0];
-  d.test = static_cast<const float*>(test); d.tb = st[0]; d.tc = st[1]; d.th = st[3]; d.tw = st[4];
-  d.grad = grad; d.gb = sg[0]; d.gc = sg[1]; d.gh = sg[3]; d.gw = sg[4];
-  d.H = H; d.W = W; d.B = B;
-  fill_display(h, d.dm);
-  return CVVDP_OK;
-}
-int cvvdp::grad_check_launch(cvvdp_handle* h) { return check_launch(h, "image_gradient"); }
-// cvvdp_video_gradient (grad_video.hip) up to the launches.  The caller's scratch, in floats, every part on a 256-byte granule, with
-// items = n_frames * batch: coef [items][4][L]; the FIR weight table [4][F][F]; three temporaries [4][items][P0]; per level d
-// [4][items][P_l] (level 0 ends up as G, what the FIR adjoint reads) and (all but the baseband) ey [items][P_l]
-namespace {
-struct GradVideoLayout { size_t coef, wt, t[3], d[CVVDP_MAX_LEVELS], ey[CVVDP_MAX_LEVELS], total; };
-// the configured clip is one the gradient exists for (what does not depend on the call order)
-bool grad_video_clip_ok(const cvvdp_handle* h) {
-  if (!h || !h->configured) return false;
-  const cvvdp_clip& c = h->c;
-  return c.is_video && c.channels == 3 && c.heatmap == CVVDP_HEATMAP_NONE && c.feature_size <= 0 && !c.defer_bands && c.block_frames >= c.n_frames &&
-         h->fuse_levels == 0 && !h->pipeline && (int64_t)c.n_frames * c.batch * 4 <= 65535;
-}
-GradVideoLayout grad_video_layout(const cvvdp_handle* h) {
-  GradVideoLayout g{};
-  const size_t F = (size_t)h->c.n_frames, items = F * (size_t)h->c.batch;
-  size_t off = 0;
-  g.coef = off; off += align_up(items * 4 * h->L);
-  g.wt = off; off += align_up(4 * F * F);
-  for (int k = 0; k < 3; ++k) { g.t[k] = off; off += align_up(4 * items * (size_t)h->lv[0].P); }
-  for (int l = 0; l < h->L; ++l) {
-    g.d[l] = off; off += align_up(4 * items * (size_t)h->lv[l].P);
-    g.ey[l] = off; if (l + 1 < h->L) off += align_up(items * (size_t)h->lv[l].P);
-  }
-  g.total = off;
-  return g;
-}
-}  // namespace
-size_t cvvdp::grad_video_scratch(const cvvdp_handle* h) { return grad_video_clip_ok(h) ? grad_video_layout(h).total * sizeof(float) : 0; }
-int cvvdp::grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes,
-                              void* scratch, size_t scratch_bytes, GradVideoPlan& plan) {
-  if (!h) return CVVDP_E_STATE;
-  if (!test || !st || !grad || !sg || !scratch) return fail(h, CVVDP_E_ARG, "video_gradient: null argument");
-  if (reinterpret_cast<uintptr_t>(test) % 4 || reinterpret_cast<uintptr_t>(grad) % 4 || reinterpret_cast<uintptr_t>(scratch) % 16)
-    return fail(h, CVVDP_E_ARG, "video_gradient: test and gradient must be 4-byte aligned, the scratch 16-byte aligned");
-  if (!h->configured) return fail(h, CVVDP_E_STATE, "video_gradient: configure first");
-  const cvvdp_clip& c = h->c;
-  if (!c.is_video) return fail(h, CVVDP_E_STATE, "video_gradient: configured for an image (cvvdp_image_gradient)");
-  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: 1-channel content is out of scope");
-  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: not with a heat map or features");
-  if (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG)
-    return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)");
-  if (c.defer_bands) return fail(h, CVVDP_E_STATE, "video_gradient: not for clips scored in pieces (defer_bands)");
-  if (c.block_frames < c.n_frames)
-    return fail(h, CVVDP_E_STATE, "video_gradient: the clip must be one temporal block (block_frames %d < n_frames %d)", c.block_frames, c.n_frames);
-  if (h->fuse_levels != 0 || h->pipeline)
-    return fail(h, CVVDP_E_STATE, "video_gradient: needs the unfused route (fuse_mode = 2), which keeps every pyramid level in the workspace");
-  const int B = c.batch, L = h->L, H = c.height, W = c.width, F = c.n_frames, fl = c.filter_len;
-  if ((int64_t)F * B * 4 > 65535)      // (4 planes per item in a grid's y)
-    return fail(h, CVVDP_E_UNSUPPORTED, "video_gradient: %d frames x %d batch items are too many (4 planes per item, 65535 at most)", F, B);
-  // the gradient's extent: the last element written is sum (size - 1) * stride over B, C, F, H, W
-  {
-    const int64_t dims[5] = {B, 3, F, H, W};
-    int64_t last = 0, term = 0;
-    bool bad = false;
-    for (int k = 0; k < 5 && !bad; ++k)
-      bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
-    if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
-      return fail(h, CVVDP_E_ARG, "video_gradient: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d x %d samples at these strides", grad_bytes,
-                  B, F, H, W);
-  }
-  const GradVideoLayout lay = grad_video_layout(h);
-  if (scratch_bytes < lay.total * sizeof(float))
-    return fail(h, CVVDP_E_ARG, "video_gradient: scratch of %zu bytes, %zu needed", scratch_bytes, lay.total * sizeof(float));
-  if (!h->ws || !h->video_scored)
-    return fail(h, CVVDP_E_STATE, "video_gradient: valid after the cvvdp_process_block that scored all %d frames from float32 frames", F);
-  float* sc = static_cast<float*>(scratch);
-  plan = GradVideoPlan{};
-  plan.L = L; plan.items = F * B;
-  GradVideoPoolArgs& po = plan.pool;
-  po.q = h->ws + h->q_off; po.coef = sc + lay.coef; po.B = B; po.F = F; po.L = L;
-  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
+// pooling over the frames of a clip: everything but coef and what the block route adds
+void fill_video_pool(const cvvdp_handle* h, GradVideoPoolArgs& po) {
+  po.q = h->ws + h->q_off; po.B = h->c.batch; po.F = h->c.n_frames; po.L = h->L;
+  for (int l = 0; l < h->L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
   for (int k = 0; k < 4; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
   po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.beta_t = h->p.beta_t; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp;
-  fill_grad_chain<4>(h, F * B, sc, lay.t, lay.d, lay.ey, po.coef, plan.band, plan.base, plan.acc);
-  // the taps as the forward applies them: tflip[c][k] multiplies window position k (F.flip(0), cvvdp_metric.py:556)
-  bool replicate = true;
-  for (int k = 0; k + 1 < fl; ++k) replicate = replicate && h->video_hist[k] == 0;
-  GradFirWeightArgs& fw = plan.fw;
-  fw.wt = sc + lay.wt; fw.F = F; fw.fl = fl;
+}
+// The temporal filter of a clip's plan.  The taps as the forward applies them: out[c][k] multiplies window position k (F.flip(0),
+// cvvdp_metric.py:556).  hist: window position k < fl - 1 -> frame of the clip, all 0 under replicate padding.
+void flipped_taps(const cvvdp_clip& c, float* out) {
   for (int ch = 0; ch < 4; ++ch)
-    for (int k = 0; k < fl; ++k) fw.tflip[ch * CVVDP_MAX_FILTER_LEN + k] = c.taps[ch * CVVDP_MAX_FILTER_LEN + (fl - 1 - k)];
-  for (int k = 0; k + 1 < fl; ++k) fw.src[k] = h->video_hist[k];
-  GradFirAdjArgs& a = plan.fir;
-  a.G = sc + lay.d[0]; a.wt = fw.wt;
+    for (int k = 0; k < c.filter_len; ++k) out[ch * CVVDP_MAX_FILTER_LEN + k] = c.taps[ch * CVVDP_MAX_FILTER_LEN + (c.filter_len - 1 - k)];
+}
+// does the adjoint need a weight table (the gather / slot variant), or do its taps fit the register window?
+bool fir_needs_table(const cvvdp_handle* h, const int16_t* hist) {
+  bool replicate = true;
+  for (int k = 0; k + 1 < h->c.filter_len; ++k) replicate = replicate && hist[k] == 0;
+  return !replicate || h->c.filter_len > CVVDP_GRAD_FIR_WL;
+}
+void fill_fir_weights(const cvvdp_handle* h, const int16_t* hist, float* wt, GradFirWeightArgs& fw) {
+  fw.wt = wt; fw.F = h->c.n_frames; fw.fl = h->c.filter_len;
+  flipped_taps(h->c, fw.tflip);
+  for (int k = 0; k + 1 < fw.fl; ++k) fw.src[k] = hist[k];
+}
+void fill_fir_adj(const cvvdp_handle* h, bool table, const float* G, const float* wt, const void* test, const int64_t st[5], float* grad, const int64_t sg[5],
+                  GradFirAdjArgs& a) {
+  const cvvdp_clip& c = h->c;
+  const int fl = c.filter_len;
+  a.G = G; a.wt = wt;
   a.test = static_cast<const float*>(test); a.tb = st[0]; a.tc = st[1]; a.tf = st[2]; a.th = st[3]; a.tw = st[4];
   a.grad = grad; a.gb = sg[0]; a.gc = sg[1]; a.gf = sg[2]; a.gh = sg[3]; a.gw = sg[4];
-  a.H = H; a.W = W; a.B = B; a.F = F; a.fl = fl;
-  a.reg_wl = (!replicate || fl > CVVDP_GRAD_FIR_WL) ? 0 : (fl <= 9 ? 9 : (fl <= 17 ? 17 : CVVDP_GRAD_FIR_WL));
+  a.H = c.height; a.W = c.width; a.B = c.batch; a.F = c.n_frames; a.fl = fl;
+  a.reg_wl = table ? 0 : (fl <= 9 ? 9 : (fl <= 17 ? 17 : CVVDP_GRAD_FIR_WL));
+  float t[4 * CVVDP_MAX_FILTER_LEN];
+  flipped_taps(c, t);
   for (int ch = 0; ch < 4; ++ch)
-    for (int k = 0; k < fl && k < CVVDP_GRAD_FIR_WL; ++k) a.tflip[ch * CVVDP_GRAD_FIR_WL + k] = fw.tflip[ch * CVVDP_MAX_FILTER_LEN + k];
+    for (int k = 0; k < fl && k < CVVDP_GRAD_FIR_WL; ++k) a.tflip[ch * CVVDP_GRAD_FIR_WL + k] = t[ch * CVVDP_MAX_FILTER_LEN + k];
   fill_display(h, a.dm);
-  return CVVDP_OK;
-}
-int cvvdp::grad_video_check_launch(cvvdp_handle* h) { return check_launch(h, "video_gradient"); }
-// cvvdp_video_gradient_blocks_begin / cvvdp_video_gradient_block (grad_blocks.hip) up to the launches.  The caller's scratch, in floats,
-// every part on a 256-byte granule, with items = block_frames * batch -- nothing in it grows with n_frames: the sums of the pooling
-// terms [batch] doubles; coef [items][4][L]; the slot variant's weights [4][fl - 1][fl]; three temporaries [4][items][P0]; per level d
-// [4][items][P_l] and (all but the baseband) ey [items][P_l]; the carry [fl][3][batch][P0]
-namespace {
-struct GradBlocksLayout { size_t sum, coef, padw, t[3], d[CVVDP_MAX_LEVELS], ey[CVVDP_MAX_LEVELS], carry, carry_floats, total; };
-bool grad_blocks_clip_ok(const cvvdp_handle* h) {
-  if (!h || !h->configured) return false;
-  const cvvdp_clip& c = h->c;
-  return c.is_video && c.channels == 3 && c.heatmap == CVVDP_HEATMAP_NONE && c.feature_size <= 0 && !c.defer_bands && h->fuse_levels == 0 &&
-         !h->pipeline && (int64_t)h->items_cap * 4 <= 65535;
-}
-GradBlocksLayout grad_blocks_layout(const cvvdp_handle* h) {
-  GradBlocksLayout g{};
-  const size_t B = (size_t)h->c.batch, items = (size_t)h->items_cap, fl = (size_t)h->c.filter_len;
-  size_t off = 0;
-  g.sum = off; off += align_up(2 * B);
-  g.coef = off; off += align_up(items * 4 * h->L);
-  g.padw = off; off += align_up(4 * (fl - 1) * fl);
-  for (int k = 0; k < 3; ++k) { g.t[k] = off; off += align_up(4 * items * (size_t)h->lv[0].P); }
-  for (int l = 0; l < h->L; ++l) {
-    g.d[l] = off; off += align_up(4 * items * (size_t)h->lv[l].P);
-    g.ey[l] = off; if (l + 1 < h->L) off += align_up(items * (size_t)h->lv[l].P);
-  }
-  g.carry_floats = fl * 3 * B * (size_t)h->lv[0].P;
-  g.carry = off; off += align_up(g.carry_floats);
-  g.total = off;
-  return g;
 }
 void grad_blocks_key(const cvvdp_handle* h, int (&key)[7]) {
   const cvvdp_clip& c = h->c;
   const int k[7] = {c.n_frames, c.batch, c.height, c.width, c.filter_len, c.block_frames, h->L};
   for (int i = 0; i < 7; ++i) key[i] = k[i];
 }
-// what both entries check of the handle and the scratch, in the order of the other gradient entries
-int grad_blocks_checks(cvvdp_handle* h, const char* what, const void* scratch, size_t scratch_bytes, bool more_null, bool misaligned) {
-  if (!h) return CVVDP_E_STATE;
-  if (!scratch || more_null) return fail(h, CVVDP_E_ARG, "%s: null argument", what);
-  if (reinterpret_cast<uintptr_t>(scratch) % 16 || misaligned)
-    return fail(h, CVVDP_E_ARG, "%s: test and gradient must be 4-byte aligned, the scratch 16-byte aligned", what);
-  if (!h->configured) return fail(h, CVVDP_E_STATE, "%s: configure first", what);
+}  // namespace
+size_t cvvdp::grad_scratch(const cvvdp_handle* h) { return grad_scratch_bytes(h, kGradImage); }
+size_t cvvdp::grad_video_scratch(const cvvdp_handle* h) { return grad_scratch_bytes(h, kGradVideo); }
+size_t cvvdp::grad_blocks_scratch(const cvvdp_handle* h) { return grad_scratch_bytes(h, kGradBlocksBlock); }
+size_t cvvdp::param_grad_scratch(const cvvdp_handle* h) { return grad_scratch_bytes(h, kGradParam); }
+int cvvdp::grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
+                        size_t scratch_bytes, GradPlan& plan) {
+  GradLayout lay;
+  if (int rc = grad_front(h, kGradImage, !test || !st || !grad || !sg || !scratch, misaligned4(test, grad) || misaligned16(scratch), st, sg, grad_bytes,
+                          scratch_bytes, lay))
+    return rc;
+  if (!h->ws || !h->image_scored) return fail(h, CVVDP_E_STATE, "image_gradient: valid after cvvdp_put_image and cvvdp_process_image");
   const cvvdp_clip& c = h->c;
-  if (!c.is_video) return fail(h, CVVDP_E_STATE, "%s: configured for an image (cvvdp_image_gradient)", what);
-  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "%s: 1-channel content is out of scope", what);
-  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "%s: not with a heat map or features", what);
-  if (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG)
-    return fail(h, CVVDP_E_UNSUPPORTED, "%s: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)", what);
-  if (c.defer_bands) return fail(h, CVVDP_E_STATE, "%s: not for clips scored in pieces (defer_bands)", what);
-  if (h->fuse_levels != 0 || h->pipeline)
-    return fail(h, CVVDP_E_STATE, "%s: needs the unfused route (fuse_mode = 2), which keeps every pyramid level in the workspace", what);
-  if ((int64_t)h->items_cap * 4 > 65535)      // (4 planes per item in a grid's y)
-    return fail(h, CVVDP_E_UNSUPPORTED, "%s: blocks of %d frames x %d batch items are too many (4 planes per item, 65535 at most)", what, c.block_frames,
-                c.batch);
+  const int B = c.batch, L = h->L;
+  float* sc = static_cast<float*>(scratch);
+  plan = GradPlan{};
+  GradPoolArgs& po = plan.pool;
+  po.q = h->ws + h->q_off; po.coef = sc + lay.coef; po.B = B; po.L = L;
+  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
+  for (int k = 0; k < 3; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
+  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp; po.image_int = h->p.image_int;
+  fill_grad_chain(h, B, sc, lay, po.coef, plan.chain);
+  GradDisplayArgs& d = plan.dsp;
+  d.tot = sc + lay.d[0];
+  d.test = static_cast<const float*>(test); d.tb = st[0]; d.tc = st[1]; d.th = st[3]; d.tw = st[4];
+  d.grad = grad; d.gb = sg[0]; d.gc = sg[1]; d.gh = sg[3]; d.gw = sg[4];
+  d.H = c.height; d.W = c.width; d.B = B;
+  fill_display(h, d.dm);
   return CVVDP_OK;
 }
-}  // namespace
-size_t cvvdp::grad_blocks_scratch(const cvvdp_handle* h) { return grad_blocks_clip_ok(h) ? grad_blocks_layout(h).total * sizeof(float) : 0; }
+int cvvdp::grad_check_launch(cvvdp_handle* h) { return check_launch(h, "image_gradient"); }
+// One temporal block: items = n_frames * batch; level 0's d ends up as G, what the FIR adjoint reads.
+int cvvdp::grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes,
+                              void* scratch, size_t scratch_bytes, GradVideoPlan& plan) {
+  GradLayout lay;
+  if (int rc = grad_front(h, kGradVideo, !test || !st || !grad || !sg || !scratch, misaligned4(test, grad) || misaligned16(scratch), st, sg, grad_bytes,
+                          scratch_bytes, lay))
+    return rc;
+  const int F = h->c.n_frames;
+  if (!h->ws || !h->video_scored)
+    return fail(h, CVVDP_E_STATE, "video_gradient: valid after the cvvdp_process_block that scored all %d frames from float32 frames", F);
+  float* sc = static_cast<float*>(scratch);
+  plan = GradVideoPlan{};
+  fill_video_pool(h, plan.pool);
+  plan.pool.coef = sc + lay.coef;
+  fill_grad_chain(h, F * h->c.batch, sc, lay, plan.pool.coef, plan.chain);
+  fill_fir_weights(h, h->video_hist, sc + lay.wt, plan.fw);
+  fill_fir_adj(h, fir_needs_table(h, h->video_hist), sc + lay.d[0], plan.fw.wt, test, st, grad, sg, plan.fir);
+  return CVVDP_OK;
+}
+int cvvdp::grad_video_check_launch(cvvdp_handle* h) { return check_launch(h, "video_gradient"); }
+// Block by block: items = the frames of the block processed last * batch.
 int cvvdp::grad_blocks_begin_prepare(cvvdp_handle* h, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan) {
-  const char* what = "video_gradient_blocks_begin";
-  if (int rc = grad_blocks_checks(h, what, scratch, scratch_bytes, false, false)) return rc;
-  const cvvdp_clip& c = h->c;
-  const GradBlocksLayout lay = grad_blocks_layout(h);
-  if (scratch_bytes < lay.total * sizeof(float)) return fail(h, CVVDP_E_ARG, "%s: scratch of %zu bytes, %zu needed", what, scratch_bytes, lay.total * sizeof(float));
+  GradLayout lay;
+  if (int rc = grad_front(h, kGradBlocksBegin, !scratch, misaligned16(scratch), nullptr, nullptr, 0, scratch_bytes, lay)) return rc;
   h->blocks_begun = false;
-  const int B = c.batch, L = h->L, F = c.n_frames, fl = c.filter_len;
+  const int B = h->c.batch, F = h->c.n_frames;
   if (!h->ws || !h->clip_hist_ok || h->last_items < 1 || h->last_items % B != 0 || h->last_q0 + h->last_items / B != F)
-    return fail(h, CVVDP_E_STATE, "%s: valid after the cvvdp_process_block calls that scored all %d frames from float32 frames handed in from frame 0 on", what, F);
+    return fail(h, CVVDP_E_STATE, "video_gradient_blocks_begin: valid after the cvvdp_process_block calls that scored all %d frames from float32 frames handed in from frame 0 on", F);
   float* sc = static_cast<float*>(scratch);
   plan = GradBlocksPlan{};
-  plan.L = L;
-  GradVideoPoolArgs& po = plan.pool.p;
-  po.q = h->ws + h->q_off; po.B = B; po.F = F; po.L = L;
-  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
-  for (int k = 0; k < 4; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
-  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.beta_t = h->p.beta_t; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp;
+  fill_video_pool(h, plan.pool.p);
   plan.pool.sum = reinterpret_cast<double*>(sc + lay.sum);
-  bool replicate = true;
-  for (int k = 0; k + 1 < fl; ++k) replicate = replicate && h->clip_hist[k] == 0;
-  plan.slots = !replicate || fl > CVVDP_GRAD_FIR_WL;
-  GradFirWeightArgs& fw = plan.fw;
-  fw.wt = sc + lay.padw; fw.F = F; fw.fl = fl;
-  for (int ch = 0; ch < 4; ++ch)
-    for (int k = 0; k < fl; ++k) fw.tflip[ch * CVVDP_MAX_FILTER_LEN + k] = c.taps[ch * CVVDP_MAX_FILTER_LEN + (fl - 1 - k)];
-  for (int k = 0; k + 1 < fl; ++k) fw.src[k] = h->clip_hist[k];
+  plan.slots = fir_needs_table(h, h->clip_hist);
+  fill_fir_weights(h, h->clip_hist, sc + lay.wt, plan.fw);
   plan.fir.carry = sc + lay.carry; plan.carry_floats = lay.carry_floats;
   return CVVDP_OK;
 }
 int cvvdp::grad_blocks_block_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes,
                                      void* scratch, size_t scratch_bytes, GradBlocksPlan& plan) {
   const char* what = "video_gradient_block";
-  if (int rc = grad_blocks_checks(h, what, scratch, scratch_bytes, !test || !st || !grad || !sg,
-                                  reinterpret_cast<uintptr_t>(test) % 4 || reinterpret_cast<uintptr_t>(grad) % 4))
+  GradLayout lay;
+  if (int rc = grad_front(h, kGradBlocksBlock, !test || !st || !grad || !sg || !scratch, misaligned4(test, grad) || misaligned16(scratch), st, sg,
+                          grad_bytes, scratch_bytes, lay))
     return rc;
-  const cvvdp_clip& c = h->c;
-  const int B = c.batch, L = h->L, H = c.height, W = c.width, F = c.n_frames, fl = c.filter_len;
-  // the gradient's extent: the last element written is sum (size - 1) * stride over B, C, F, H, W of the whole clip
-  {
-    const int64_t dims[5] = {B, 3, F, H, W};
-    int64_t last = 0, term = 0;
-    bool bad = false;
-    for (int k = 0; k < 5 && !bad; ++k)
-      bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
-    if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
-      return fail(h, CVVDP_E_ARG, "%s: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d x %d samples at these strides", what, grad_bytes, B, F,
-                  H, W);
-  }
-  const GradBlocksLayout lay = grad_blocks_layout(h);
-  if (scratch_bytes < lay.total * sizeof(float)) return fail(h, CVVDP_E_ARG, "%s: scratch of %zu bytes, %zu needed", what, scratch_bytes, lay.total * sizeof(float));
+  const int B = h->c.batch, F = h->c.n_frames;
   int key[7];
   grad_blocks_key(h, key);
   if (!h->blocks_begun || std::memcmp(key, h->blocks_key, sizeof key) != 0)
@@ -1329,33 +1298,16 @@ int cvvdp::grad_blocks_block_prepare(cvvdp_handle* h, const void* test, const in
   const int items = h->last_items, n = items / B, q0 = h->last_q0;
   float* sc = static_cast<float*>(scratch);
   plan = GradBlocksPlan{};
-  plan.L = L; plan.items = items;
-  GradVideoPoolArgs& po = plan.pool.p;
-  po.q = h->ws + h->q_off; po.coef = sc + lay.coef; po.B = B; po.F = F; po.L = L;
-  for (int l = 0; l < L; ++l) po.n_px[l] = (int32_t)h->lv[l].P;
-  for (int k = 0; k < 4; ++k) { po.ch_w[k] = h->p.ch_w[k]; po.bb_w[k] = h->p.baseband_weight[k]; }
-  po.beta_sch = h->p.beta_sch; po.beta_tch = h->p.beta_tch; po.beta_t = h->p.beta_t; po.jod_a = h->p.jod_a; po.jod_exp = h->p.jod_exp;
+  fill_video_pool(h, plan.pool.p);
+  plan.pool.p.coef = sc + lay.coef;
   plan.pool.sum = reinterpret_cast<double*>(sc + lay.sum); plan.pool.q0 = q0; plan.pool.n = n;
-  fill_grad_chain<4>(h, items, sc, lay.t, lay.d, lay.ey, po.coef, plan.band, plan.base, plan.acc);
-  bool replicate = true;
-  for (int k = 0; k + 1 < fl; ++k) replicate = replicate && h->clip_hist[k] == 0;
-  plan.slots = !replicate || fl > CVVDP_GRAD_FIR_WL;
+  fill_grad_chain(h, items, sc, lay, plan.pool.p.coef, plan.chain);
+  plan.slots = fir_needs_table(h, h->clip_hist);
   GradFirStreamArgs& s = plan.fir;
-  s.carry = sc + lay.carry; s.padw = sc + lay.padw; s.f0 = q0; s.n = n;
+  s.carry = sc + lay.carry; s.padw = sc + lay.wt; s.f0 = q0; s.n = n;
   plan.carry_floats = lay.carry_floats;
-  GradFirAdjArgs& a = s.a;
-  a.G = sc + lay.d[0]; a.wt = nullptr;
-  a.test = static_cast<const float*>(test); a.tb = st[0]; a.tc = st[1]; a.tf = st[2]; a.th = st[3]; a.tw = st[4];
-  a.grad = grad; a.gb = sg[0]; a.gc = sg[1]; a.gf = sg[2]; a.gh = sg[3]; a.gw = sg[4];
-  a.H = H; a.W = W; a.B = B; a.F = F; a.fl = fl;
-  a.reg_wl = plan.slots ? 0 : (fl <= 9 ? 9 : (fl <= 17 ? 17 : CVVDP_GRAD_FIR_WL));
-  for (int ch = 0; ch < 4; ++ch)
-    for (int k = 0; k < fl; ++k) {
-      const float t = c.taps[ch * CVVDP_MAX_FILTER_LEN + (fl - 1 - k)];      // as the forward applies them (F.flip(0), cvvdp_metric.py:556)
-      s.tfull[ch * CVVDP_MAX_FILTER_LEN + k] = t;
-      if (k < CVVDP_GRAD_FIR_WL) a.tflip[ch * CVVDP_GRAD_FIR_WL + k] = t;
-    }
-  fill_display(h, a.dm);
+  flipped_taps(h->c, s.tfull);
+  fill_fir_adj(h, plan.slots, sc + lay.d[0], nullptr, test, st, grad, sg, s.a);
   return CVVDP_OK;
 }
 int cvvdp::grad_blocks_check_launch(cvvdp_handle* h, bool block) {
@@ -1366,70 +1318,26 @@ int cvvdp::grad_blocks_check_launch(cvvdp_handle* h, bool block) {
   if (h->blocks_next >= h->c.n_frames) h->blocks_begun = false;      // the clip's last block has flushed the carry
   return rc;
 }
-// cvvdp_param_gradient (grad_param.hip) up to the launches.  The caller's scratch, every part on a 256-byte granule, sized for a full
-// block (items = block_frames * batch; 1 * batch for an image) of NC = 3 / 4 channels: coef [items][NC][L] floats; two temporaries
-// [NC][items][P0] floats; the slab [batch][block_frames * R][24] doubles, R = sum over the Laplacian levels of ceil(P_l / 2048), + 1
-namespace {
-struct ParamLayout { size_t coef, t[2], slab, total; int nblk[CVVDP_MAX_LEVELS], row_off[CVVDP_MAX_LEVELS], rows_frame; };
-bool param_clip_ok(const cvvdp_handle* h) {
-  if (!h || !h->configured) return false;
-  const cvvdp_clip& c = h->c;
-  return c.channels == 3 && c.heatmap == CVVDP_HEATMAP_NONE && c.feature_size <= 0 && !c.defer_bands &&
-         (!c.is_video || (h->fuse_levels == 0 && !h->pipeline)) && (int64_t)h->items_cap * h->nch <= 65535;
-}
-ParamLayout param_layout(const cvvdp_handle* h) {
-  ParamLayout g{};
-  const size_t items = (size_t)h->items_cap, NC = (size_t)h->nch;
-  size_t off = 0;
-  g.coef = off; off += align_up(items * NC * h->L);
-  for (int k = 0; k < 2; ++k) { g.t[k] = off; off += align_up(NC * items * (size_t)h->lv[0].P); }
-  int rows = 0;
-  for (int l = 0; l < h->L; ++l) {
-    g.nblk[l] = l + 1 < h->L ? (int)((h->lv[l].P + CVVDP_PARAM_BLOCK_PX - 1) / CVVDP_PARAM_BLOCK_PX) : 1;
-    g.row_off[l] = rows; rows += g.nblk[l];
-  }
-  g.rows_frame = rows;
-  g.slab = off; off += align_up(items * (size_t)rows * CVVDP_PARAM_GRAD_COUNT * 2);      // (doubles: two floats each)
-  g.total = off;
-  return g;
-}
-}  // namespace
-size_t cvvdp::param_grad_scratch(const cvvdp_handle* h) { return param_clip_ok(h) ? param_layout(h).total * sizeof(float) : 0; }
+// The parameters' gradient of the block processed last, 3 (image) or 4 (video) channels: the chain's first steps per level, then the slab.
 int cvvdp::param_grad_prepare(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, ParamPlan& plan) {
-  if (!h) return CVVDP_E_STATE;
-  if (!dq || !acc || !scratch) return fail(h, CVVDP_E_ARG, "param_gradient: null argument");
-  if (reinterpret_cast<uintptr_t>(dq) % 4 || reinterpret_cast<uintptr_t>(acc) % 8 || reinterpret_cast<uintptr_t>(scratch) % 16)
-    return fail(h, CVVDP_E_ARG, "param_gradient: dq must be 4-byte aligned, acc 8-byte aligned, the scratch 16-byte aligned");
-  if (!h->configured) return fail(h, CVVDP_E_STATE, "param_gradient: configure first");
+  GradLayout lay;
+  if (int rc = grad_front(h, kGradParam, !dq || !acc || !scratch, reinterpret_cast<uintptr_t>(dq) % 4 || reinterpret_cast<uintptr_t>(acc) % 8 || misaligned16(scratch),
+                          nullptr, nullptr, 0, scratch_bytes, lay))
+    return rc;
   const cvvdp_clip& c = h->c;
-  if (c.channels != 3) return fail(h, CVVDP_E_UNSUPPORTED, "param_gradient: 1-channel content is out of scope");
-  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return fail(h, CVVDP_E_UNSUPPORTED, "param_gradient: not with a heat map or features");
-  if (c.defer_bands) return fail(h, CVVDP_E_STATE, "param_gradient: not for clips scored in pieces (defer_bands)");
-  if (c.is_video && (h->fuse_levels != 0 || h->pipeline))
-    return fail(h, CVVDP_E_STATE, "param_gradient: needs the unfused route (fuse_mode = 2), which keeps every pyramid level in the workspace");
   const int NC = h->nch, L = h->L, B = c.batch;
-  if ((int64_t)h->items_cap * NC > 65535)      // (NC planes per item in a grid's y)
-    return fail(h, CVVDP_E_UNSUPPORTED, "param_gradient: %d frames x %d batch items are too many (%d planes per item, 65535 at most)",
-                c.is_video ? c.block_frames : 1, B, NC);
-  const ParamLayout lay = param_layout(h);
-  if (scratch_bytes < lay.total * sizeof(float))
-    return fail(h, CVVDP_E_ARG, "param_gradient: scratch of %zu bytes, %zu needed", scratch_bytes, lay.total * sizeof(float));
   if (!h->ws || h->last_items < 1 || h->last_item0 != 0 || h->last_items % B != 0 || (!c.is_video && !h->image_scored))
     return fail(h, CVVDP_E_STATE, c.is_video ? "param_gradient: valid after a cvvdp_process_block" : "param_gradient: valid after cvvdp_put_image and cvvdp_process_image");
   float* sc = static_cast<float*>(scratch);
   const int items = h->last_items, n_frames = items / B;
   plan = ParamPlan{};
-  plan.NC = NC; plan.L = L; plan.items = items;
+  plan.NC = NC;
   ParamCoefArgs& co = plan.coef;
   co.dq = dq; co.q = h->ws + h->q_off; co.coef = sc + lay.coef;
   co.B = B; co.NC = NC; co.count = c.n_frames; co.L = L; co.n_frames = n_frames; co.q0 = h->last_q0;
   for (int l = 0; l < L; ++l) co.n_px[l] = (int32_t)h->lv[l].P;
-  // the chain's arguments; of its three temporaries the third, the per-level outputs and the pyramid adjoints are not used here
-  const size_t t[3] = {lay.t[0], lay.t[1], lay.t[0]};
-  const size_t none[CVVDP_MAX_LEVELS] = {};
-  GradAccumArgs unused[CVVDP_MAX_LEVELS];
-  if (NC == 3) fill_grad_chain<3>(h, items, sc, t, none, none, co.coef, plan.band3, plan.base3, unused);
-  else fill_grad_chain<4>(h, items, sc, t, none, none, co.coef, plan.band4, plan.base4, unused);
+  if (NC == 3) fill_grad_chain(h, items, sc, lay, co.coef, plan.chain3);
+  else fill_grad_chain(h, items, sc, lay, co.coef, plan.chain4);
   double* slab = reinterpret_cast<double*>(sc + lay.slab);
   const int64_t rows_b = (int64_t)lay.rows_frame * n_frames;
   for (int l = 0; l < L; ++l) {

@@ -141,9 +141,10 @@ void blur_pass(const float* in, float* out, int H, int W, int planes, bool verti
 
 // levels finest first, the baseband, then the totals coarsest first: B items of NC channels (NC * B planes fit a grid's y: core.cpp checks)
 template <int NC>
-void launch_chain(int L, int B, const GradBandArgsT<NC>* band, const GradBaseArgsT<NC>& base, const GradAccumArgs* acc, hipStream_t s) {
+void launch_chain(const GradChain<NC>& c, hipStream_t s) {
+  const int L = c.L, B = c.items;
   for (int l = 0; l + 1 < L; ++l) {
-    const GradBandArgsT<NC>& a = band[l];
+    const GradBandArgsT<NC>& a = c.band[l];
     const dim3 grid = pixel_grid(a.H, a.W, B);
     hipLaunchKernelGGL(k_grad_min<NC>, grid, dim3(GT), 0, s, a);
     if (a.blur) {
@@ -157,8 +158,8 @@ void launch_chain(int L, int B, const GradBandArgsT<NC>* band, const GradBaseArg
     }
     hipLaunchKernelGGL(k_grad_contrast<NC>, grid, dim3(GT), 0, s, a);
   }
-  hipLaunchKernelGGL(k_grad_base<NC>, dim3(B), dim3(256), 0, s, base);
-  for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum<NC>, pixel_grid(acc[l].H, acc[l].W, B), dim3(GT), 0, s, acc[l]);
+  hipLaunchKernelGGL(k_grad_base<NC>, dim3(B), dim3(256), 0, s, c.base);
+  for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum<NC>, pixel_grid(c.acc[l].H, c.acc[l].W, B), dim3(GT), 0, s, c.acc[l]);
 }
 
 }  // namespace
@@ -166,13 +167,11 @@ void launch_chain(int L, int B, const GradBandArgsT<NC>* band, const GradBaseArg
 void launch_image_gradient(const GradPlan& p, hipStream_t s) {
   const int B = p.pool.B;
   hipLaunchKernelGGL(k_grad_pool, dim3((B + 63) / 64), dim3(64), 0, s, p.pool);
-  launch_chain<3>(p.L, B, p.band, p.base, p.acc, s);
+  launch_chain<3>(p.chain, s);
   hipLaunchKernelGGL(k_grad_display, pixel_grid(p.dsp.H, p.dsp.W, B), dim3(GT), 0, s, p.dsp);
 }
 
-void launch_grad_chain4(int L, int items, const GradBandArgsT<4>* band, const GradBaseArgsT<4>& base, const GradAccumArgs* acc, hipStream_t s) {
-  launch_chain<4>(L, items, band, base, acc, s);
-}
+void launch_grad_chain4(const GradChain<4>& c, hipStream_t s) { launch_chain<4>(c, s); }
 
 // the parameter gradient (grad_param.hip) runs the first steps of a level's chain: the same kernels, launched as launch_chain does
 void launch_grad_min3(const GradBandArgsT<3>& a, hipStream_t s) { hipLaunchKernelGGL(k_grad_min<3>, pixel_grid(a.H, a.W, a.B), dim3(GT), 0, s, a); }
@@ -190,15 +189,9 @@ size_t cvvdp_image_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp:
 
 int cvvdp_image_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                          size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
-  cvvdp::GradPlan* p = new (std::nothrow) cvvdp::GradPlan;      // (tens of kilobytes: not on the stack)
-  if (!p) return CVVDP_E_ARG;
-  int rc = cvvdp::grad_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, *p);
-  if (rc == CVVDP_OK) {
-    cvvdp::launch_image_gradient(*p, static_cast<hipStream_t>(stream));
-    rc = cvvdp::grad_check_launch(h);
-  }
-  delete p;
-  return rc;
+  return cvvdp::run_plan<cvvdp::GradPlan>(
+      [&](auto& p) { return cvvdp::grad_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
+      [&](auto& p) { cvvdp::launch_image_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_check_launch(h); });
 }
 
 }  // extern "C"

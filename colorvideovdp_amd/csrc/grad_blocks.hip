@@ -107,8 +107,8 @@ void launch_grad_blocks_begin(const GradBlocksPlan& p, hipStream_t s) {
 
 void launch_grad_blocks_block(const GradBlocksPlan& p, hipStream_t s) {
   const GradFirAdjArgs& f = p.fir.a;
-  hipLaunchKernelGGL(k_blocks_vpool_coef, dim3((unsigned)((p.items + VT - 1) / VT)), dim3(VT), 0, s, p.pool);
-  launch_grad_chain4(p.L, p.items, p.band, p.base, p.acc, s);
+  hipLaunchKernelGGL(k_blocks_vpool_coef, dim3((unsigned)((p.chain.items + VT - 1) / VT)), dim3(VT), 0, s, p.pool);
+  launch_grad_chain4(p.chain, s);
   const unsigned px = (unsigned)(((int64_t)f.H * f.W + VT - 1) / VT);
   if (p.slots) {
     hipLaunchKernelGGL(k_blocks_fir_slots, dim3(px, f.B), dim3(VT), 0, s, p.fir);
@@ -129,28 +129,16 @@ extern "C" {
 size_t cvvdp_video_gradient_blocks_scratch_bytes(const cvvdp_handle* h) { return cvvdp::grad_blocks_scratch(h); }
 
 int cvvdp_video_gradient_blocks_begin(cvvdp_handle* h, void* dev_scratch, size_t scratch_bytes, void* stream) {
-  cvvdp::GradBlocksPlan* p = new (std::nothrow) cvvdp::GradBlocksPlan;      // (tens of kilobytes: not on the stack)
-  if (!p) return CVVDP_E_ARG;
-  int rc = cvvdp::grad_blocks_begin_prepare(h, dev_scratch, scratch_bytes, *p);
-  if (rc == CVVDP_OK) {
-    cvvdp::launch_grad_blocks_begin(*p, static_cast<hipStream_t>(stream));
-    rc = cvvdp::grad_blocks_check_launch(h, false);
-  }
-  delete p;
-  return rc;
+  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_begin_prepare(h, dev_scratch, scratch_bytes, p); },
+                                                [&](auto& p) { cvvdp::launch_grad_blocks_begin(p, static_cast<hipStream_t>(stream)); },
+                                                [&] { return cvvdp::grad_blocks_check_launch(h, false); });
 }
 
 int cvvdp_video_gradient_block(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                                size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
-  cvvdp::GradBlocksPlan* p = new (std::nothrow) cvvdp::GradBlocksPlan;
-  if (!p) return CVVDP_E_ARG;
-  int rc = cvvdp::grad_blocks_block_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, *p);
-  if (rc == CVVDP_OK) {
-    cvvdp::launch_grad_blocks_block(*p, static_cast<hipStream_t>(stream));
-    rc = cvvdp::grad_blocks_check_launch(h, true);
-  }
-  delete p;
-  return rc;
+  return cvvdp::run_plan<cvvdp::GradBlocksPlan>(
+      [&](auto& p) { return cvvdp::grad_blocks_block_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
+      [&](auto& p) { cvvdp::launch_grad_blocks_block(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_blocks_check_launch(h, true); });
 }
 
 }  // extern "C"

@@ -110,24 +110,24 @@ __global__ __launch_bounds__(CVVDP_PARAM_LANES * 32) void k_param_reduce(const P
 }
 
 template <int NC>
-void launch_levels(const ParamPlan& p, const GradBandArgsT<NC>* band, const GradBaseArgsT<NC>& base, hipStream_t s) {
-  for (int l = 0; l + 1 < p.L; ++l) {
-    const GradBandArgsT<NC>& a = band[l];
+void launch_levels(const ParamPlan& p, const GradChain<NC>& c, hipStream_t s) {
+  for (int l = 0; l + 1 < c.L; ++l) {
+    const GradBandArgsT<NC>& a = c.band[l];
     if constexpr (NC == 3) launch_grad_min3(a, s); else launch_grad_min4(a, s);
     if (a.blur) {
       launch_grad_blur_fwd(a.t0, a.t1, a.H, a.W, NC * a.B, true, a.taps, s);
       launch_grad_blur_fwd(a.t1, a.t0, a.H, a.W, NC * a.B, false, a.taps, s);
     }
-    hipLaunchKernelGGL(k_param_point<NC>, dim3((unsigned)p.rows[l].nblk, (unsigned)p.items), dim3(PT), 0, s, a, p.rows[l]);
+    hipLaunchKernelGGL(k_param_point<NC>, dim3((unsigned)p.rows[l].nblk, (unsigned)c.items), dim3(PT), 0, s, a, p.rows[l]);
   }
-  hipLaunchKernelGGL(k_param_base<NC>, dim3((unsigned)p.items), dim3(PT), 0, s, base, p.rows[p.L - 1]);
+  hipLaunchKernelGGL(k_param_base<NC>, dim3((unsigned)c.items), dim3(PT), 0, s, c.base, p.rows[c.L - 1]);
 }
 
 void launch_param_gradient(const ParamPlan& p, hipStream_t s) {
-  const int n = p.items * p.NC * p.L;
+  const int n = p.coef.n_frames * p.coef.B * p.NC * p.coef.L;
   hipLaunchKernelGGL(k_param_coef, dim3((n + PT - 1) / PT), dim3(PT), 0, s, p.coef);
-  if (p.NC == 3) launch_levels<3>(p, p.band3, p.base3, s);
-  else launch_levels<4>(p, p.band4, p.base4, s);
+  if (p.NC == 3) launch_levels<3>(p, p.chain3, s);
+  else launch_levels<4>(p, p.chain4, s);
   hipLaunchKernelGGL(k_param_reduce, dim3((unsigned)p.coef.B), dim3(CVVDP_PARAM_LANES * 32), 0, s, p.red);
 }
 
@@ -141,15 +141,9 @@ extern "C" {
 size_t cvvdp_param_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp::param_grad_scratch(h); }
 
 int cvvdp_param_gradient(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
-  cvvdp::ParamPlan* p = new (std::nothrow) cvvdp::ParamPlan;      // (tens of kilobytes: not on the stack)
-  if (!p) return CVVDP_E_ARG;
-  int rc = cvvdp::param_grad_prepare(h, dq, acc, scratch, scratch_bytes, *p);
-  if (rc == CVVDP_OK) {
-    cvvdp::launch_param_gradient(*p, static_cast<hipStream_t>(stream));
-    rc = cvvdp::param_grad_check_launch(h);
-  }
-  delete p;
-  return rc;
+  return cvvdp::run_plan<cvvdp::ParamPlan>([&](auto& p) { return cvvdp::param_grad_prepare(h, dq, acc, scratch, scratch_bytes, p); },
+                                           [&](auto& p) { cvvdp::launch_param_gradient(p, static_cast<hipStream_t>(stream)); },
+                                           [&] { return cvvdp::param_grad_check_launch(h); });
 }
 
 }  // extern "C"

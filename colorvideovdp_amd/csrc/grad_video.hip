@@ -109,7 +109,7 @@ __global__ __launch_bounds__(VT) void k_grad_fir_gather(const GradFirAdjArgs a) 
 void launch_video_gradient(const GradVideoPlan& p, hipStream_t s) {
   const GradFirAdjArgs& f = p.fir;
   hipLaunchKernelGGL(k_grad_vpool, dim3(p.pool.B), dim3(VT), 0, s, p.pool);
-  launch_grad_chain4(p.L, p.items, p.band, p.base, p.acc, s);
+  launch_grad_chain4(p.chain, s);
   const unsigned px = (unsigned)(((int64_t)f.H * f.W + VT - 1) / VT);
   if (f.reg_wl == 0) {
     const int64_t n = (int64_t)4 * f.F * f.F;
@@ -133,15 +133,9 @@ size_t cvvdp_video_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp:
 
 int cvvdp_video_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                          size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
-  cvvdp::GradVideoPlan* p = new (std::nothrow) cvvdp::GradVideoPlan;      // (tens of kilobytes: not on the stack)
-  if (!p) return CVVDP_E_ARG;
-  int rc = cvvdp::grad_video_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, *p);
-  if (rc == CVVDP_OK) {
-    cvvdp::launch_video_gradient(*p, static_cast<hipStream_t>(stream));
-    rc = cvvdp::grad_video_check_launch(h);
-  }
-  delete p;
-  return rc;
+  return cvvdp::run_plan<cvvdp::GradVideoPlan>(
+      [&](auto& p) { return cvvdp::grad_video_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
+      [&](auto& p) { cvvdp::launch_video_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_video_check_launch(h); });
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <memory>
+#include <new>
 #include "../../include/cvvdp_hip.h"
 
 namespace cvvdp {
@@ -654,14 +656,28 @@ struct GradDisplayArgs {     // total of level 0 -> dJOD/dV, written through the
   int32_t H, W, B;
   DisplayArgs dm;
 };
+template <int NC>
+struct GradChain {           // the band chain of every gradient plan: levels finest first, the baseband, the totals coarsest first
+  int32_t L, items;
+  GradBandArgsT<NC> band[CVVDP_MAX_LEVELS];  // levels 0 .. L - 2
+  GradBaseArgsT<NC> base;
+  GradAccumArgs acc[CVVDP_MAX_LEVELS];       // (left empty by the parameter gradient, which stops before the pyramid adjoints)
+};
 struct GradPlan {            // everything cvvdp_image_gradient launches, filled by core.cpp
-  int32_t L;
   GradPoolArgs pool;
-  GradBandArgs band[CVVDP_MAX_LEVELS];      // levels 0 .. L - 2
-  GradBaseArgs base;
-  GradAccumArgs acc[CVVDP_MAX_LEVELS];
+  GradChain<3> chain;
   GradDisplayArgs dsp;
 };
+// A C ABI entry of the gradient routes: the plan (tens of kilobytes: not on the stack), filled by prepare(plan); then launch(plan) and
+// what check() says of the launches
+template <class Plan, class Prepare, class Launch, class Check>
+int run_plan(Prepare prepare, Launch launch, Check check) {
+  const std::unique_ptr<Plan> p(new (std::nothrow) Plan);
+  if (!p) return CVVDP_E_ARG;
+  int rc = prepare(*p);
+  if (rc == CVVDP_OK) { launch(*p); rc = check(); }
+  return rc;
+}
 static_assert(sizeof(GradBandArgsT<4>) <= 4096 && sizeof(GradDisplayArgs) <= 4096, "kernel arguments of the gradient kernels");
 // core.cpp: scratch size of the configured clip (0: no gradient for it), argument / state checks and the plan; the error of a launch
 size_t grad_scratch(const cvvdp_handle* h);
@@ -699,11 +715,8 @@ struct GradFirAdjArgs {      // G = dJOD/d(level-0 planes) -> dJOD/dV through FI
   DisplayArgs dm;
 };
 struct GradVideoPlan {       // everything cvvdp_video_gradient launches, filled by core.cpp
-  int32_t L, items;
   GradVideoPoolArgs pool;
-  GradBandArgsT<4> band[CVVDP_MAX_LEVELS];
-  GradBaseArgsT<4> base;
-  GradAccumArgs acc[CVVDP_MAX_LEVELS];
+  GradChain<4> chain;
   GradFirWeightArgs fw;
   GradFirAdjArgs fir;
 };
@@ -713,7 +726,7 @@ int grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], f
                        size_t scratch_bytes, GradVideoPlan& plan);
 int grad_video_check_launch(cvvdp_handle* h);
 // grad.hip: the band chain (levels, baseband, pyramid adjoints) for 4 channels; grad_video.hip: pooling and the FIR / display adjoint
-void launch_grad_chain4(int L, int items, const GradBandArgsT<4>* band, const GradBaseArgsT<4>& base, const GradAccumArgs* acc, hipStream_t s);
+void launch_grad_chain4(const GradChain<4>& c, hipStream_t s);
 void launch_video_gradient(const GradVideoPlan& p, hipStream_t s);
 
 // ---------------------------------------------------------------- gradient of the video JOD, block by block (grad_blocks.hip)
@@ -733,12 +746,9 @@ struct GradFirStreamArgs {
   float tfull[4 * CVVDP_MAX_FILTER_LEN];     // slot variant: [c][k] multiplies window position k
 };
 struct GradBlocksPlan {      // everything cvvdp_video_gradient_blocks_begin / _block launch, filled by core.cpp
-  int32_t L, items;
   bool slots;               // the slot variant of the streamed adjoint (symmetric padding, or a filter beyond the register window)
   GradBlocksPoolArgs pool;
-  GradBandArgsT<4> band[CVVDP_MAX_LEVELS];
-  GradBaseArgsT<4> base;
-  GradAccumArgs acc[CVVDP_MAX_LEVELS];
+  GradChain<4> chain;       // (block only)
   GradFirWeightArgs fw;     // fw.wt = padw
   GradFirStreamArgs fir;
   size_t carry_floats;
@@ -772,12 +782,10 @@ struct ParamRowArgs {        // where the blocks of one level put their rows: sl
 };
 struct ParamReduceArgs { const double* slab; double* acc; int64_t rows_b; };
 struct ParamPlan {           // everything cvvdp_param_gradient launches, filled by core.cpp
-  int32_t NC, L, items;
+  int32_t NC;               // which of the two chains is filled
   ParamCoefArgs coef;
-  GradBandArgsT<3> band3[CVVDP_MAX_LEVELS];
-  GradBandArgsT<4> band4[CVVDP_MAX_LEVELS];
-  GradBaseArgsT<3> base3;
-  GradBaseArgsT<4> base4;
+  GradChain<3> chain3;
+  GradChain<4> chain4;
   ParamRowArgs rows[CVVDP_MAX_LEVELS];
   ParamReduceArgs red;
 };

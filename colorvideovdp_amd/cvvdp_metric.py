@@ -17,6 +17,7 @@ Differences that are deliberate:
 """
 import collections
 import concurrent.futures
+import contextlib
 import ctypes
 import json
 import math
@@ -702,19 +703,54 @@ class cvvdp(vq_metric):
         vs = video_source_array(t, r, 0, dim_order="BCFHW", display_photometry=self.display_photometry)
         Q, _, _ = self._score_range(vs, 0, 1)
         jod = self.do_pooling_and_jods(Q)
-        lib = _capi.lib()
+        grad, _, call = self._pixel_gradient_entry("cvvdp_image_gradient", _capi.lib().cvvdp_image_gradient_scratch_bytes, test, t, dim_order)
+        call()
+        return jod.squeeze(), grad
+
+    @contextlib.contextmanager
+    def _borrowed(self, **settings):
+        """What a gradient call sets for itself (fuse_mode, block_frames, _pixel_grad_plan, _param_grad_plan), put back on every exit path
+        together with the hook the second walk runs after each block.  Yields no_memory(text): a guard under which an allocation that
+        fails gives up the workspace and raises a vq_exception with text()."""
+        saved = {k: getattr(self, k, False) for k in settings}
+        for k, v in settings.items():
+            setattr(self, k, v)
+
+        @contextlib.contextmanager
+        def no_memory(text):
+            try:
+                yield
+            except torch.cuda.OutOfMemoryError:
+                self._ws = None
+                raise vq_exception(text()) from None
+
+        try:
+            yield no_memory
+        finally:
+            for k, v in saved.items():
+                setattr(self, k, v)
+            self._block_hook = None
+
+    def _pixel_gradient_entry(self, name, scratch_bytes, test, t, dim_order, guard=None):
+        """Everything between the forward and the C entry `name` of a pixel gradient; t is the BCFHW view of test on the device.  Returns
+        grad, float32 with the shape of `test`; the scratch of scratch_bytes(handle) bytes, allocated under `guard` (stream-ordered: the
+        caching allocator may hand it out again once the kernels are queued); and call(stream=None), which runs the entry on the stream
+        (None: torch's current one) and checks it."""
         grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
         gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
         assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
-        need = lib.cvvdp_image_gradient_scratch_bytes(self._handle)
-        scratch = torch.empty(max(int(need), 16), dtype=torch.uint8, device=self.device)
+        with guard or contextlib.nullcontext():
+            scratch = torch.empty(max(int(scratch_bytes(self._handle)), 16), dtype=torch.uint8, device=self.device)
         st = (ctypes.c_int64 * 5)(*t.stride())
         sg = (ctypes.c_int64 * 5)(*gv.stride())
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = lib.cvvdp_image_gradient(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(), scratch.numel(), stream)
-        _capi.check(self._handle, rc, "cvvdp_image_gradient")
-        del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
-        return jod.squeeze(), grad
+        entry = getattr(_capi.lib(), name)
+
+        def call(stream=None):
+            stream = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+            rc = entry(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(), scratch.numel(), stream)
+            _capi.check(self._handle, rc, name)
+
+        return grad, scratch, call
 
     def _predict_video_with_gradient(self, test, t, r, dim_order, frames_per_second):
         """predict_with_gradient for a clip: t, r are the BCFHW views on the device."""
@@ -722,32 +758,20 @@ class cvvdp(vq_metric):
             raise vq_exception("predict_with_gradient: not available with frame sharding")
         lib = _capi.lib()
         n_frames = int(t.shape[2])
-        saved = (self.fuse_mode, self.block_frames)
-        self.fuse_mode, self.block_frames = 2, n_frames          # one temporal block on the route that keeps every pyramid level
-        scratch = None
-        try:
+
+        def text():
+            ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_scratch_bytes(self._handle))
+            return (f"predict_with_gradient: the clip needs a workspace of {ws} bytes and a scratch of {sc} bytes as one temporal block, "
+                    "which cannot be allocated on this device")
+
+        # one temporal block on the route that keeps every pyramid level
+        with self._borrowed(fuse_mode=2, block_frames=n_frames) as no_memory:
             vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
-            try:
+            with no_memory(text):
                 Q, _, _ = self._score_range(vs, 0, n_frames)
-                need = int(lib.cvvdp_video_gradient_scratch_bytes(self._handle))
-                scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
-            except torch.cuda.OutOfMemoryError:
-                ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_scratch_bytes(self._handle))
-                self._ws = None
-                raise vq_exception(f"predict_with_gradient: the clip needs a workspace of {ws} bytes and a scratch of {sc} bytes as one temporal block, "
-                                   "which cannot be allocated on this device") from None
-            jod = self.do_pooling_and_jods(Q)
-            grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
-            gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
-            assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
-            st = (ctypes.c_int64 * 5)(*t.stride())
-            sg = (ctypes.c_int64 * 5)(*gv.stride())
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = lib.cvvdp_video_gradient(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(), scratch.numel(), stream)
-            _capi.check(self._handle, rc, "cvvdp_video_gradient")
-        finally:
-            self.fuse_mode, self.block_frames = saved
-            del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
+            grad, _, call = self._pixel_gradient_entry("cvvdp_video_gradient", lib.cvvdp_video_gradient_scratch_bytes, test, t, dim_order, no_memory(text))
+            jod = self.do_pooling_and_jods(Q)       # (reads Q back: after the allocations, which then overlap the forward)
+            call()
         return jod.squeeze(), grad
 
     def _predict_video_with_gradient_blocks(self, test, t, r, dim_order, frames_per_second, block_frames):
@@ -757,47 +781,29 @@ class cvvdp(vq_metric):
             raise vq_exception("predict_with_gradient: not available with frame sharding")
         lib = _capi.lib()
         n_frames = int(t.shape[2])
-        saved = (self.fuse_mode, self.block_frames)
-        auto = block_frames == "auto"
-        self.fuse_mode, self.block_frames = 2, (None if auto else min(int(block_frames), n_frames))
-        self._pixel_grad_plan = True         # (_pick_block_frames counts the backward's scratch when it sizes the blocks itself)
-        scratch = None
-        try:
+
+        def text():
+            ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_blocks_scratch_bytes(self._handle))
+            return (f"predict_with_gradient: blocks of {self.last_block_frames} frames need a workspace of {ws} bytes and a scratch of "
+                    f"{sc} bytes, which cannot be allocated on this device")
+
+        # (_pixel_grad_plan: _pick_block_frames counts the backward's scratch when it sizes the blocks itself)
+        with self._borrowed(fuse_mode=2, block_frames=None if block_frames == "auto" else min(int(block_frames), n_frames), _pixel_grad_plan=True) as no_memory:
             vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
-            try:
+            with no_memory(text):
                 Q, _, _ = self._score_range(vs, 0, n_frames)                   # pass 1: the normal block loop
                 self.block_frames = int(self.last_block_frames)                # (pass 2 walks the same blocks, whatever is free by then)
-                need = int(lib.cvvdp_video_gradient_blocks_scratch_bytes(self._handle))
-                scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
-            except torch.cuda.OutOfMemoryError:
-                ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_blocks_scratch_bytes(self._handle))
-                self._ws = None
-                raise vq_exception(f"predict_with_gradient: blocks of {self.last_block_frames} frames need a workspace of {ws} bytes and a scratch of "
-                                   f"{sc} bytes, which cannot be allocated on this device") from None
-            jod = self.do_pooling_and_jods(Q)
-            grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
-            gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
-            assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
-            st = (ctypes.c_int64 * 5)(*t.stride())
-            sg = (ctypes.c_int64 * 5)(*gv.stride())
+            grad, scratch, after_block = self._pixel_gradient_entry("cvvdp_video_gradient_block", lib.cvvdp_video_gradient_blocks_scratch_bytes, test, t,
+                                                                    dim_order, no_memory(text))
+            jod = self.do_pooling_and_jods(Q)       # (reads Q back: after the allocations, which then overlap the forward)
             stream = torch.cuda.current_stream(self.device).cuda_stream
             rc = lib.cvvdp_video_gradient_blocks_begin(self._handle, scratch.data_ptr(), scratch.numel(), stream)
             _capi.check(self._handle, rc, "cvvdp_video_gradient_blocks_begin")
-
-            def after_block(stream):
-                rc = lib.cvvdp_video_gradient_block(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(),
-                                                    scratch.numel(), stream)
-                _capi.check(self._handle, rc, "cvvdp_video_gradient_block")
-
             if n_frames <= int(self.last_block_frames):
                 after_block(stream)                                             # one block: its pyramid is still in the workspace
             else:
                 self._block_hook = after_block                                  # pass 2: the same blocks again, the entry after each
                 self._score_range(vs, 0, n_frames)
-        finally:
-            self.fuse_mode, self.block_frames = saved
-            self._pixel_grad_plan, self._block_hook = False, None
-            del scratch        # stream-ordered: the caching allocator may hand it out again once the kernels are queued
         return jod.squeeze(), grad
 
     def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None):
@@ -866,15 +872,13 @@ class cvvdp(vq_metric):
         src_dm = getattr(vid_source, "dm_photometry", None)
         swap = src_dm is not None and src_dm is not self.display_photometry and self._is_raw_source(vid_source)
         prev_dm = self.display_photometry
-        saved = self.fuse_mode
         if swap:
             self.display_photometry = src_dm
             self._make_handle()
-        self.fuse_mode, self._param_grad_plan = 2, True
         try:
-            return self._parameter_gradient(vid_source, what)
+            with self._borrowed(fuse_mode=2, _param_grad_plan=True):
+                return self._parameter_gradient(vid_source, what)
         finally:
-            self.fuse_mode, self._param_grad_plan, self._block_hook = saved, False, None
             if swap:
                 self.display_photometry = prev_dm
                 self._make_handle()
@@ -914,10 +918,7 @@ class cvvdp(vq_metric):
             after_block(torch.cuda.current_stream(self.device).cuda_stream)     # one block: its pyramid is still in the workspace
         else:
             self._block_hook = after_block                                      # pass 2: the same blocks again, the entry after each
-            try:
-                self._score_range(vs, 0, n_frames)
-            finally:
-                self._block_hook = None
+            self._score_range(vs, 0, n_frames)
         band = acc.to(torch.float32)
         for n, (a, b) in BAND_PARAMETERS.items():
             grads[n] = band[:, a:b].reshape((B,) + tuple(np.shape(p[n]))).contiguous()

@@ -6,8 +6,11 @@
 //   * the hip* calls succeed and do nothing (streams / events are counted so that leaks show up),
 //   * every launch_* stub checks that each buffer the kernel would touch lies inside the bound workspace (extents derived from
 //     the struct's own geometry), that strips x segments cover the level, and that the tables are within their arrays.
-// The driver sweeps a few thousand random clip configurations (sizes 2..4500, every frame rate, block sizes, heat-map modes,
-// features mode, batches, shards) through the whole call sequence of the Python mirror.  Exit code 0 = no finding.
+//   * the five gradient prepares (image, one-block video, begin / block of the block-by-block route, parameters) are called after
+//     a clip they accept was scored, with a fake scratch of exactly the size the route asks for: every pointer of every kernel
+//     argument lies in the scratch, the workspace or the caller's buffers, the scratch's regions lie apart, one byte less is refused.
+// The driver sweeps a few thousand random clip configurations (sizes 2..4500 and beyond, every frame rate, block sizes, heat-map
+// modes, features mode, batches, shards) through the whole call sequence of the Python mirror.  Exit code 0 = no finding.
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
 //       colorvideovdp_amd/csrc/core.cpp tests/native/host_sanitize.cpp -o host_sanitize && ./host_sanitize [n_cases] [seed]
@@ -16,6 +19,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
+#include <memory>
 #include <random>
 #include <vector>
 #include "../../colorvideovdp_amd/csrc/kernels.h"
@@ -47,6 +52,7 @@ static char g_case[256];
 
 [[noreturn]] static void die(const char* fmt, ...) {
   va_list ap; va_start(ap, fmt);
+  fflush(stdout);
   fprintf(stderr, "host_sanitize: FINDING in case {%s}: ", g_case);
   vfprintf(stderr, fmt, ap); fprintf(stderr, "\n");
   va_end(ap);
@@ -211,6 +217,219 @@ void launch_heat_colour(const HeatArgs& a, hipStream_t) { chk_heat(a); }
 
 }  // namespace cvvdp
 
+// ---------------------------------------------------------------- gradient plans
+// The five prepares of core.cpp fill whole plans; nothing is launched.  Every pointer of every kernel argument must lie, with the extent
+// the kernel indexes, inside the caller's scratch, the workspace, or the buffer it was handed; and the regions of one plan inside the
+// scratch (a region = what starts at one address) must not run into each other.
+struct Buf { const char* name; uintptr_t lo; size_t bytes; };
+static Buf g_scratch{"scratch", uintptr_t(5) << 44, 0}, g_test{"test", uintptr_t(7) << 44, 0}, g_grad{"gradient", uintptr_t(9) << 44, 0},
+    g_dq{"dq", uintptr_t(11) << 44, 0}, g_acc{"acc", uintptr_t(13) << 44, 0};
+struct Span { uintptr_t lo, hi; const char* what; };
+static std::vector<Span> g_spans;
+static void in_buf(const Buf& b, const void* p, size_t bytes, const char* what) {
+  ++g_checks;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  if (!p) die("%s: null", what);
+  if (a < b.lo || a + bytes > b.lo + b.bytes) die("%s: bytes [%lld, %lld) outside the %s of %zu", what, (long long)(a - b.lo), (long long)(a - b.lo + bytes), b.name, b.bytes);
+}
+static void in_scratch(const void* p, size_t n_floats, const char* what) {
+  in_buf(g_scratch, p, n_floats * sizeof(float), what);
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(p), hi = lo + n_floats * sizeof(float);
+  if (lo == hi) return;
+  for (Span& s : g_spans) {
+    if (s.lo != lo) continue;
+    REQUIRE(!strcmp(s.what, what), "scratch regions %s and %s start at the same address", s.what, what);
+    if (hi > s.hi) s.hi = hi;      // (the temporaries are sized for level 0 and used by every level)
+    return;
+  }
+  g_spans.push_back(Span{lo, hi, what});
+}
+static void spans_disjoint() {
+  for (size_t i = 0; i < g_spans.size(); ++i)
+    for (size_t j = i + 1; j < g_spans.size(); ++j)
+      REQUIRE(g_spans[i].hi <= g_spans[j].lo || g_spans[j].hi <= g_spans[i].lo, "scratch regions overlap: %s [%llx, %llx) and %s [%llx, %llx)", g_spans[i].what,
+              (unsigned long long)g_spans[i].lo, (unsigned long long)g_spans[i].hi, g_spans[j].what, (unsigned long long)g_spans[j].lo, (unsigned long long)g_spans[j].hi);
+  g_spans.clear();
+}
+// the farthest element a kernel reaches through the caller's strides
+static size_t strided_bytes(int B, int F, int H, int W, int64_t sb, int64_t sc, int64_t sf, int64_t sh, int64_t sw) {
+  return (size_t)((B - 1) * sb + 2 * sc + (F - 1) * sf + (H - 1) * sh + (W - 1) * sw + 1) * sizeof(float);
+}
+namespace cvvdp {
+// outputs: the chain writes d / ey and runs the pyramid adjoints (the parameter gradient stops before them and reads neither t2, d nor ey)
+template <int NC>
+static void chk_chain(const GradChain<NC>& c, bool outputs) {
+  const int L = c.L, B = c.items;
+  REQUIRE(L >= 1 && L <= CVVDP_MAX_LEVELS && B >= 1 && B * NC <= 65535, "chain: %d levels, %d items of %d planes", L, B, NC);
+  for (int l = 0; l + 1 < L; ++l) {
+    const GradBandArgsT<NC>& a = c.band[l];
+    const size_t P = (size_t)a.H * a.W, Pc = (size_t)a.Hc * a.Wc;
+    REQUIRE(a.B == B && a.L == L && a.level == l && a.Hc == (a.H + 1) / 2 && a.Wc == (a.W + 1) / 2, "chain level %d: geometry", l);
+    in_ws(a.g, (size_t)(2 * NC - 1) * a.gps + B * P, "chain g"); in_ws(a.gc, (size_t)(2 * NC - 1) * a.gcps + B * Pc, "chain gc");
+    in_scratch(a.coef, (size_t)B * NC * L, "coef"); in_scratch(a.t0, NC * B * P, "t0"); in_scratch(a.t1, NC * B * P, "t1");
+    if (outputs) { in_scratch(a.t2, NC * B * P, "t2"); in_scratch(a.d, NC * B * P, "d"); in_scratch(a.ey, B * P, "ey"); }
+  }
+  const GradBaseArgsT<NC>& b = c.base;
+  REQUIRE(b.B == B && b.L == L && b.level == L - 1, "chain baseband: geometry");
+  in_ws(b.g, (size_t)(2 * NC - 1) * b.gps + (size_t)B * b.H * b.W, "chain baseband g"); in_scratch(b.coef, (size_t)B * NC * L, "coef");
+  if (!outputs) return;
+  in_scratch(b.d, (size_t)NC * B * b.H * b.W, "d");
+  for (int l = 0; l < L; ++l) {
+    const GradAccumArgs& a = c.acc[l];
+    REQUIRE(a.B == B && (l == 0) == !a.d_f && (l == 0) == !a.ey_f && (l + 1 == L) == !a.tot_c, "chain total %d: which neighbours", l);
+    in_scratch(a.d, (size_t)NC * B * a.H * a.W, "d");
+    if (a.d_f) { REQUIRE(a.H == (a.Hf + 1) / 2 && a.W == (a.Wf + 1) / 2, "chain total %d: finer level", l); in_scratch(a.d_f, (size_t)NC * B * a.Hf * a.Wf, "d"); in_scratch(a.ey_f, (size_t)B * a.Hf * a.Wf, "ey"); }
+    if (a.tot_c) { REQUIRE(a.Hc == (a.H + 1) / 2 && a.Wc == (a.W + 1) / 2, "chain total %d: coarser level", l); in_scratch(a.tot_c, (size_t)NC * B * a.Hc * a.Wc, "d"); }
+  }
+}
+static void chk_plan(const GradPlan& p) {
+  ++g_launches;
+  const GradPoolArgs& po = p.pool;
+  in_ws(po.q, (size_t)po.B * 3 * po.L, "image pool Q_per_ch"); in_scratch(po.coef, (size_t)po.B * 3 * po.L, "coef");
+  REQUIRE(po.B == p.chain.items && po.L == p.chain.L, "image plan: pool and chain disagree");
+  chk_chain(p.chain, true);
+  const GradDisplayArgs& d = p.dsp;
+  chk_display(d.dm);
+  in_scratch(d.tot, (size_t)3 * d.B * d.H * d.W, "d");
+  in_buf(g_test, d.test, strided_bytes(d.B, 1, d.H, d.W, d.tb, d.tc, 0, d.th, d.tw), "image test"); in_buf(g_grad, d.grad, strided_bytes(d.B, 1, d.H, d.W, d.gb, d.gc, 0, d.gh, d.gw), "image gradient");
+  spans_disjoint();
+}
+static void chk_vpool(const GradVideoPoolArgs& po, int coef_items) {
+  in_ws(po.q, (size_t)po.B * 4 * po.F * po.L, "video pool Q_per_ch");
+  if (coef_items) in_scratch(po.coef, (size_t)coef_items * 4 * po.L, "coef");
+}
+static void chk_fir_adj(const GradFirAdjArgs& a, int items) {
+  chk_display(a.dm);
+  REQUIRE(a.fl >= 1 && a.fl <= CVVDP_MAX_FILTER_LEN && (a.reg_wl == 0 || (a.reg_wl >= a.fl && a.reg_wl <= CVVDP_GRAD_FIR_WL)), "fir adjoint: fl %d, window %d", a.fl, a.reg_wl);
+  in_scratch(a.G, (size_t)4 * items * a.H * a.W, "d");
+  in_buf(g_test, a.test, strided_bytes(a.B, a.F, a.H, a.W, a.tb, a.tc, a.tf, a.th, a.tw), "clip test"); in_buf(g_grad, a.grad, strided_bytes(a.B, a.F, a.H, a.W, a.gb, a.gc, a.gf, a.gh, a.gw), "clip gradient");
+}
+static void chk_fir_weights(const GradFirWeightArgs& w, size_t n_floats) {
+  in_scratch(w.wt, n_floats, "wt");
+  for (int k = 0; k + 1 < w.fl; ++k) REQUIRE(w.src[k] >= 0 && w.src[k] < w.F, "fir weights: window position %d reads frame %d of %d", k, w.src[k], w.F);
+}
+static void chk_plan(const GradVideoPlan& p) {
+  ++g_launches;
+  const GradFirAdjArgs& f = p.fir;
+  REQUIRE(p.chain.items == f.F * f.B && p.pool.F == f.F && p.pool.B == f.B, "video plan: items");
+  chk_vpool(p.pool, p.chain.items);
+  chk_chain(p.chain, true);
+  if (f.reg_wl == 0) { chk_fir_weights(p.fw, (size_t)4 * f.F * f.F); REQUIRE(f.wt == p.fw.wt && p.fw.F == f.F && p.fw.fl == f.fl, "video plan: weight table"); }
+  chk_fir_adj(f, p.chain.items);
+  spans_disjoint();
+}
+static void chk_plan_begin(const GradBlocksPlan& p) {
+  ++g_launches;
+  chk_vpool(p.pool.p, 0);
+  in_scratch(p.pool.sum, (size_t)2 * p.pool.p.B, "sum");
+  if (p.slots && p.fw.fl > 1) chk_fir_weights(p.fw, (size_t)4 * (p.fw.fl - 1) * p.fw.fl);
+  in_scratch(p.fir.carry, p.carry_floats, "carry");
+  spans_disjoint();
+}
+static void chk_plan_block(const GradBlocksPlan& p) {
+  ++g_launches;
+  const GradFirStreamArgs& s = p.fir;
+  const GradFirAdjArgs& f = s.a;
+  REQUIRE(p.chain.items == s.n * f.B && p.pool.n == s.n && p.pool.q0 == s.f0 && s.f0 >= 0 && s.f0 + s.n <= f.F, "block plan: frames [%d, %d) of %d", s.f0, s.f0 + s.n, f.F);
+  REQUIRE(p.slots == (f.reg_wl == 0), "block plan: variant");
+  chk_vpool(p.pool.p, p.chain.items);
+  in_scratch(p.pool.sum, (size_t)2 * f.B, "sum");
+  chk_chain(p.chain, true);
+  chk_fir_adj(f, p.chain.items);
+  in_scratch(s.carry, (size_t)f.fl * 3 * f.B * f.H * f.W, "carry");
+  REQUIRE(p.carry_floats == (size_t)f.fl * 3 * f.B * f.H * f.W, "block plan: carry of %zu floats", p.carry_floats);
+  if (p.slots && f.fl > 1) in_scratch(s.padw, (size_t)4 * (f.fl - 1) * f.fl, "wt");
+  spans_disjoint();
+}
+static void chk_plan(const ParamPlan& p) {
+  ++g_launches;
+  const ParamCoefArgs& co = p.coef;
+  const int items = co.n_frames * co.B;
+  REQUIRE((p.NC == 3 || p.NC == 4) && co.NC == p.NC && co.q0 >= 0 && co.q0 + co.n_frames <= co.count, "param plan: %d channels, frames [%d, %d) of %d", p.NC, co.q0, co.q0 + co.n_frames, co.count);
+  const size_t nq = (size_t)co.B * co.NC * co.count * co.L;
+  in_buf(g_dq, co.dq, nq * sizeof(float), "param dq"); in_ws(co.q, nq, "param Q_per_ch"); in_scratch(co.coef, (size_t)items * co.NC * co.L, "coef");
+  if (p.NC == 3) { REQUIRE(p.chain3.items == items && p.chain3.L == co.L, "param plan: chain"); chk_chain(p.chain3, false); }
+  else { REQUIRE(p.chain4.items == items && p.chain4.L == co.L, "param plan: chain"); chk_chain(p.chain4, false); }
+  for (int l = 0; l < co.L; ++l) {
+    const ParamRowArgs& r = p.rows[l];
+    REQUIRE(r.B == co.B && r.n_frames == co.n_frames && r.nblk >= 1 && (int64_t)(r.row_off + r.nblk) * r.n_frames <= r.rows_b, "param rows of level %d", l);
+    in_scratch(r.slab, (size_t)r.B * r.rows_b * CVVDP_PARAM_GRAD_COUNT * 2, "slab");
+  }
+  REQUIRE(p.red.rows_b == p.rows[0].rows_b, "param reduce: rows");
+  in_scratch(p.red.slab, (size_t)co.B * p.red.rows_b * CVVDP_PARAM_GRAD_COUNT * 2, "slab");
+  in_buf(g_acc, p.red.acc, (size_t)co.B * CVVDP_PARAM_GRAD_COUNT * sizeof(double), "param acc");
+  spans_disjoint();
+}
+}  // namespace cvvdp
+
+// One route of a scored case: nothing to do where the configured clip has no scratch size; a scratch one byte short must be refused;
+// with exactly the size, the plan is checked if the call is accepted (it is refused for the display, or for how the clip was scored).
+static long g_route[5], g_levels_seen[CVVDP_MAX_LEVELS + 1], g_fl_side[2], g_padding[2], g_cuts[4];
+template <class Plan, class Prepare, class Check>
+static bool grad_route(int route, cvvdp_handle* h, size_t need, Prepare prepare, Check check) {
+  if (need == 0) return false;
+  static const std::unique_ptr<Plan> plan(new Plan);      // (tens of kilobytes: not on the stack)
+  g_scratch.bytes = need - 1;
+  REQUIRE(prepare(need - 1, *plan) != CVVDP_OK, "route %d: a scratch one byte short of %zu was accepted", route, need);
+  g_scratch.bytes = need;
+  if (prepare(need, *plan) != CVVDP_OK) { REQUIRE(cvvdp_last_error(h)[0] != 0, "refusal without a message"); return false; }
+  check(*plan);
+  ++g_route[route];
+  return true;
+}
+
+// The gradient entries after a clip was scored, in the order of the Python mirror: the image's or the one-block clip's gradient and the
+// parameters' gradient of the block processed last; then begin, and the clip's blocks once more with the two per-block entries after each.
+static void check_gradients(cvvdp_handle* h, const cvvdp_clip& c, const int64_t st[5], float* ws, size_t ws_bytes, const void* src, const std::vector<int32_t>& hs0) {
+  using namespace cvvdp;
+  const size_t clip_floats = (size_t)c.batch * 3 * c.n_frames * c.height * c.width;
+  g_test.bytes = g_grad.bytes = clip_floats * sizeof(float);
+  g_dq.bytes = (size_t)c.batch * (c.is_video ? 4 : 3) * c.n_frames * c.n_levels * sizeof(float); g_acc.bytes = (size_t)c.batch * CVVDP_PARAM_GRAD_COUNT * sizeof(double);
+  void* const sc = reinterpret_cast<void*>(g_scratch.lo);
+  const void* const test = reinterpret_cast<const void*>(g_test.lo);
+  float* const grad = reinterpret_cast<float*>(g_grad.lo);
+  auto param = [&] {
+    return grad_route<ParamPlan>(4, h, param_grad_scratch(h), [&](size_t n, ParamPlan& p) { return param_grad_prepare(h, reinterpret_cast<const float*>(g_dq.lo), reinterpret_cast<double*>(g_acc.lo), sc, n, p); },
+                                 [](const ParamPlan& p) { chk_plan(p); });
+  };
+  auto block = [&] {
+    return grad_route<GradBlocksPlan>(3, h, grad_blocks_scratch(h), [&](size_t n, GradBlocksPlan& p) { return grad_blocks_block_prepare(h, test, st, grad, st, g_grad.bytes, sc, n, p); },
+                                      [](const GradBlocksPlan& p) { chk_plan_block(p); });
+  };
+  bool any = param();
+  if (!c.is_video) {
+    any |= grad_route<GradPlan>(0, h, grad_scratch(h), [&](size_t n, GradPlan& p) { return grad_prepare(h, test, st, grad, st, g_grad.bytes, sc, n, p); }, [](const GradPlan& p) { chk_plan(p); });
+    g_levels_seen[c.n_levels] += any;
+    return;
+  }
+  const int M = c.filter_len - 1;
+  bool replicate = true;
+  for (int i = 0; i < M; ++i) replicate = replicate && hs0[i] == 0;
+  const bool one = grad_route<GradVideoPlan>(1, h, grad_video_scratch(h), [&](size_t n, GradVideoPlan& p) { return grad_video_prepare(h, test, st, grad, st, g_grad.bytes, sc, n, p); },
+                                             [](const GradVideoPlan& p) { chk_plan(p); });
+  const bool begun = grad_route<GradBlocksPlan>(2, h, grad_blocks_scratch(h), [&](size_t n, GradBlocksPlan& p) { return grad_blocks_begin_prepare(h, sc, n, p); },
+                                                [](const GradBlocksPlan& p) { chk_plan_begin(p); });
+  g_levels_seen[c.n_levels] += any || one || begun;
+  if (one || begun) { ++g_fl_side[c.filter_len > CVVDP_GRAD_FIR_WL]; ++g_padding[replicate]; }
+  if (!begun) return;
+  REQUIRE(!block(), "a block's gradient was accepted before begin had run");
+  REQUIRE(grad_blocks_check_launch(h, false) == CVVDP_OK, "begin: %s", cvvdp_last_error(h));
+  REQUIRE(cvvdp_configure(h, &c) == CVVDP_OK && cvvdp_bind_workspace(h, ws, ws_bytes) == CVVDP_OK, "the second walk's configure: %s", cvvdp_last_error(h));
+  int n_blocks = 0;
+  for (int done = 0; done < c.n_frames; ++n_blocks) {
+    const int n = std::min(c.block_frames, c.n_frames - done);
+    std::vector<int32_t> hs(hs0);
+    for (int i = 0; i < M && done > 0; ++i) hs[i] = c.raw_halo ? (done + i) % n : -1 - i;
+    REQUIRE(cvvdp_process_block(h, src, src, CVVDP_F32, st, st, 0, hs.data(), n, done, nullptr) == CVVDP_OK, "the second walk's block at %d: %s", done, cvvdp_last_error(h));
+    (void)param();
+    REQUIRE(block(), "the gradient of the block at frame %d was refused: %s", done, cvvdp_last_error(h));
+    REQUIRE(grad_blocks_check_launch(h, true) == CVVDP_OK, "block: %s", cvvdp_last_error(h));
+    REQUIRE(!block(), "the block at frame %d was accepted twice", done);
+    done += n;
+  }
+  ++g_cuts[std::min(n_blocks, 4) - 1];
+}
+
 // ---------------------------------------------------------------- driver
 static cvvdp_params make_params(std::mt19937& rng) {
   cvvdp_params p{};
@@ -279,6 +498,7 @@ int main(int argc, char** argv) {
   void* const fake_out = reinterpret_cast<void*>(uintptr_t(3) << 44);
   for (int k = 0; k < n_cases; ++k) {
     cvvdp_params p = make_params(rng);
+    if (ri(0, 1)) { const int differentiable[3] = {CVVDP_EOTF_SRGB, CVVDP_EOTF_LINEAR, CVVDP_EOTF_GAMMA}; p.eotf = differentiable[ri(0, 2)]; }
     cvvdp_handle* h = nullptr;
     REQUIRE(cvvdp_create(&p, &h) == CVVDP_OK && h, "create failed");
     const int reuse = ri(1, 3);                       // a handle is re-configured between clips, like the Python mirror does
@@ -305,7 +525,20 @@ int main(int argc, char** argv) {
       c.feature_size = (c.heatmap == 0 && ri(0, 3) == 0) ? ri(1, 90) : 0;
       c.fuse_mode = ri(0, 5) == 0 ? ri(0, 3) : 0;                                        // 3: out of range, must be refused
       c.band_layout = ri(0, 7) == 0 ? ri(0, 2) : 0;                                      // 2: out of range
-      if (c.is_video && ri(0, 3) == 0) { c.defer_bands = 1; c.score_frames = ri(0, c.block_frames + 1); }   // 0 and block + 1: out of range
+      // half the clips are ones the gradient routes accept: three channels, no heat map, features or pieces, float32 frames from frame 0
+      // on the unfused route; short enough for several cuts into blocks, one block among them; any number of levels
+      const bool gradable = ri(0, 1) == 0, replicate = ri(0, 1) == 0;
+      if (gradable) {
+        c.channels = 3; c.heatmap = 0; c.feature_size = 0; c.first_frame = 0; c.fuse_mode = 2 * ri(0, 1);
+        if (c.is_video) { c.total_frames = c.n_frames = ri(1, 80); c.block_frames = ri(0, 1) ? c.n_frames : ri(1, c.n_frames); }
+        if (ri(0, 3) == 0) c.n_levels = ri(1, CVVDP_MAX_LEVELS);
+        if (ri(0, 11) == 0) {      // the deepest pyramids: every level but the last needs two rows and two columns
+          c.n_levels = ri(CVVDP_MAX_LEVELS - 4, CVVDP_MAX_LEVELS);
+          c.width = ri((1 << (c.n_levels - 1)) + 1, 46000); c.height = ri((1 << (c.n_levels - 1)) + 1, 46000); c.batch = 1;
+          if (c.is_video) c.total_frames = c.n_frames = c.block_frames = ri(1, 3);
+        }
+      }
+      if (!gradable && c.is_video && ri(0, 3) == 0) { c.defer_bands = 1; c.score_frames = ri(0, c.block_frames + 1); }   // 0 and block + 1: out of range
       for (int i = 0; i < 4 * CVVDP_MAX_FILTER_LEN; ++i) c.taps[i] = 0.01f * (i % 7);
       for (auto& v : c.csf_rows) v = 1.0f;
       snprintf(g_case, sizeof g_case, "#%d %dx%d B%d C%d video %d fl %d frames %d/%d block %d levels %d heat %d dump %d halo %d fs %d eotf %d", k, c.width,
@@ -320,6 +553,7 @@ int main(int argc, char** argv) {
       if (ri(0, 4) == 0) (void)cvvdp_profile_enable(h, 1);
       const int64_t st[5] = {(int64_t)3 * c.n_frames * c.height * c.width, (int64_t)c.n_frames * c.height * c.width, (int64_t)c.height * c.width, c.width, 1};
       int rc = CVVDP_OK;
+      std::vector<int32_t> hs0(std::max(c.filter_len - 1, 1));      // the padding map of the clip's first block
       if (!c.is_video) {
         rc = cvvdp_put_image(h, fake_src, fake_src, ri(0, 3), st, st, nullptr);
         if (rc == CVVDP_OK) rc = cvvdp_process_image(h, nullptr);
@@ -331,7 +565,10 @@ int main(int argc, char** argv) {
           const int n = std::min(c.block_frames, c.n_frames - done);
           std::vector<int32_t> hs(std::max(M, 1));
           for (int i = 0; i < M; ++i) hs[i] = (done == 0 || c.raw_halo) ? ri(0, n - 1) : -1 - i;     // padding / real halo frames, or the DKL tail
-          const int kind = ri(0, 5);
+          if (done == 0) hs0 = hs;
+          if (done == 0 && gradable && replicate) std::fill(hs0.begin(), hs0.end(), 0);
+          if (done == 0) hs = hs0;
+          const int kind = gradable ? 2 : ri(0, 5);
           if (kind == 0 && c.channels == 3 && c.batch == 1 && c.width % 2 == 0 && c.height % 2 == 0) {
             cvvdp_yuv_format f{}; f.chroma = 420; f.bit_depth = ri(0, 1) ? 8 : 10; f.matrix = ri(0, 1) ? 709 : 2020;
             f.frame_stride_test = f.frame_stride_ref = (int64_t)c.width * c.height * 3 / 2;
@@ -339,7 +576,7 @@ int main(int argc, char** argv) {
           } else if (kind == 1) {
             rc = cvvdp_process_block_filtered(h, fake_src, fake_src, st, st, n, done, nullptr);
           } else {
-            rc = cvvdp_process_block(h, fake_src, fake_src, ri(0, 4), st, st, 0, hs.data(), n, done, nullptr);
+            rc = cvvdp_process_block(h, fake_src, fake_src, gradable ? (int)CVVDP_F32 : ri(0, 4), st, st, 0, hs.data(), n, done, nullptr);
           }
           if (rc == CVVDP_OK && c.defer_bands) {
             // the block is filtered: bands and heat maps piece by piece, then what must be refused
@@ -368,6 +605,7 @@ int main(int argc, char** argv) {
       (void)cvvdp_profile_read(h, ms, cnt);
       (void)cvvdp_profile_enable(h, 0);
       for (int w = 0; w <= CVVDP_BUF_Q; ++w) { void* ptr = nullptr; size_t nf = 0; if (cvvdp_debug_buffer(h, w, 0, &ptr, &nf) == CVVDP_OK) in_ws(ptr, nf, "debug buffer"); }
+      check_gradients(h, c, st, fake_ws, bytes, fake_src, hs0);
       ++ran;
     }
     cvvdp_destroy(h);
@@ -376,6 +614,14 @@ int main(int argc, char** argv) {
   // null / misuse paths return codes, never crash
   REQUIRE(cvvdp_configure(nullptr, nullptr) != CVVDP_OK && cvvdp_workspace_bytes(nullptr) == 0, "null handle accepted");
   cvvdp_destroy(nullptr);
+  printf("host_sanitize: gradient plans checked: image %ld, video %ld, begin %ld, block %ld, param %ld\n", g_route[0], g_route[1], g_route[2], g_route[3], g_route[4]);
+  printf("host_sanitize: ... of 1 .. %d levels:", CVVDP_MAX_LEVELS);
+  for (int l = 1; l <= CVVDP_MAX_LEVELS; ++l) printf(" %ld", g_levels_seen[l]);
+  printf("\n");
+  for (int l = 1; l <= CVVDP_MAX_LEVELS; ++l) REQUIRE(g_levels_seen[l] > 0, "no gradient plan of %d levels", l);
+  REQUIRE(g_fl_side[0] && g_fl_side[1] && g_padding[0] && g_padding[1], "gradient plans: filters up to / beyond %d taps %ld / %ld, symmetric / replicate padding %ld / %ld",
+          cvvdp::CVVDP_GRAD_FIR_WL, g_fl_side[0], g_fl_side[1], g_padding[0], g_padding[1]);
+  REQUIRE(g_cuts[0] && g_cuts[1] && g_cuts[2] && g_cuts[3], "gradient plans: clips of 1 / 2 / 3 / more blocks %ld / %ld / %ld / %ld", g_cuts[0], g_cuts[1], g_cuts[2], g_cuts[3]);
   printf("host_sanitize: %d handles, %ld clips run, %ld refused, %ld launches checked, %ld buffer extents inside their workspace, 0 findings\n",
          n_cases, ran, refused, g_launches, g_checks);
   return ran > n_cases / 2 ? 0 : 2;
