@@ -117,6 +117,7 @@ PREVIEW_PIXEL_BYTES = {PREVIEW_F32: 12, PREVIEW_RGBE: 4, PREVIEW_RGB48: 6}
 ML_WEIGHTS, ML_FEATURE_NET_OFFSET = 9368, 7924               # CVVDP_ML_WEIGHTS, CVVDP_ML_FEATURE_NET_OFFSET
 MT_WEIGHTS, MT_CHUNK_TOKENS = 3166468, 32768                 # CVVDP_MT_WEIGHTS, CVVDP_MT_CHUNK_TOKENS
 PARAM_GRAD_COUNT = 24                                        # CVVDP_PARAM_GRAD_COUNT
+POOL_THETA_COUNT = 9                                         # CVVDP_POOL_THETA_COUNT
 
 DUMP_TEMPORAL, DUMP_LPYR, DUMP_DIFF = range(3)              # CVVDP_DUMP_*
 DUMP = {"temporal": DUMP_TEMPORAL, "lpyr": DUMP_LPYR, "difference": DUMP_DIFF}
@@ -196,6 +197,9 @@ SYMBOLS = {
                                              C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_param_gradient_scratch_bytes": (C.c_size_t, [C.c_void_p]),
     "cvvdp_param_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_pool_dataset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double),
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cvvdp_pool_dataset_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvvdp_preview_args_size": (C.c_int32, []),
     "cvvdp_pixel_preview": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(PreviewArgs), C.c_void_p, C.c_size_t, C.c_void_p]),

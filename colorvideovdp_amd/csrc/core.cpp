@@ -1348,6 +1348,9 @@ int cvvdp::param_grad_prepare(cvvdp_handle* h, const float* dq, double* acc, voi
   return CVVDP_OK;
 }
 int cvvdp::param_grad_check_launch(cvvdp_handle* h) { return check_launch(h, "param_gradient"); }
+// cvvdp_pool_dataset / cvvdp_pool_dataset_loss (pool_dataset.hip) use the handle for the error text alone
+int cvvdp::pool_dataset_fail(cvvdp_handle* h, const char* text) { return fail(h, CVVDP_E_ARG, "%s", text); }
+int cvvdp::pool_dataset_check_launch(cvvdp_handle* h, const char* what) { return check_launch(h, what); }
 // cvvdp_pixel_preview (preview.hip) up to the launch: the source checks of cvvdp_pixel_sse on one side, then the target, the format and
 // the canvas.  Nothing is launched unless the last pixel of the last frame lies inside dst_bytes.
 int cvvdp::preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref,

@@ -797,4 +797,9 @@ void launch_grad_min3(const GradBandArgsT<3>& a, hipStream_t s);
 void launch_grad_min4(const GradBandArgsT<4>& a, hipStream_t s);
 void launch_grad_blur_fwd(const float* in, float* out, int H, int W, int planes, bool vertical, const float* w, hipStream_t s);
 
+// ---------------------------------------------------------------- dataset pooling for calibration (pool_dataset.hip, pool_dataset_dev.h)
+// The entries check their arguments themselves; core.cpp keeps the error text (CVVDP_E_ARG) and reads the launch's status.
+int pool_dataset_fail(cvvdp_handle* h, const char* text);
+int pool_dataset_check_launch(cvvdp_handle* h, const char* what);
+
 }  // namespace cvvdp

@@ -890,6 +890,7 @@ class cvvdp(vq_metric):
         if self._route_channels != 3:
             raise vq_exception(f"{what}: 1-channel content is out of scope, the content must have three colour channels")
         jod = self.do_pooling_and_jods(Q)
+        self._param_grad_Q = Q                                             # the Q_per_ch that was scored (calibration's rescoring mode pools it again)
         B = int(Q.shape[0])
         p = self.parameters
         # the pooling stage in float64 on the host (a few thousand numbers): its parameters' gradients and dJOD/dQ_per_ch in one autograd call

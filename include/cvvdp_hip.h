@@ -569,6 +569,34 @@ int cvvdp_video_gradient_block(cvvdp_handle* h, const void* dev_test, const int6
 size_t cvvdp_param_gradient_scratch_bytes(const cvvdp_handle* h);
 int cvvdp_param_gradient(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Dataset pooling for calibration (the loop of calibration/train.py:135-147, which calls do_pooling_and_jods once per clip per step):
+ * the JOD of n clips of a ragged, packed set of Q_per_ch and d JOD / d theta of each, in one launch and in float64.  It computes
+ * do_pooling_and_jods + met2jod (cvvdp_metric.py:597-658; get_ch_weights :604-607, the baseband weight :617-619, lp_norm over bands :625
+ * and channels :633 with safe_pow :83-86 and no normalisation, image_int :636, the normalised norm over frames :638, met2jod :646-658
+ * with the linear branch for Q <= 0.1), as colorvideovdp_amd.cvvdp_metric.pool_jod_float64 states them.
+ *   dev_q       fp32; clip k starts at float dev_offset[k] (int64) and is laid out [C][F][L]
+ *   dev_shape   int32 [clips][3] = C, F, L.  The caller guarantees C in 1..4, L in 1..CVVDP_MAX_LEVELS, F >= 1 and that every clip lies inside
+ *               dev_q (the arrays are on the device: the entry cannot look)
+ *   dev_index   int32 [n]: row i is clip dev_index[i] (a mini-batch); null: rows are clips 0 .. n-1
+ *   dev_theta   9 doubles ON THE DEVICE: ch_chrom_w, ch_trans_w, baseband_weight[0..3], jod_a, jod_exp, image_int.  Channel c is weighted by
+ *               the c-th of (1, ch_chrom_w, ch_chrom_w, ch_trans_w), for C = 1 and 2 as well (:604-607 slices the four)
+ *   beta        host: beta_sch, beta_tch, beta_t
+ *   dev_jod     double [n];  dev_grad  double [n][9] = d JOD / d theta.  Entries that cannot act are exactly 0: image_int for F > 1,
+ *               ch_trans_w for C < 4, ch_chrom_w for C == 1, baseband_weight[c] for c >= C
+ * One 256-thread workgroup per row; thread t adds frames t, t + 256, .. in ascending order, then the 64-lane shuffle tree, then the four
+ * waves in order: no atomics, the same bits on every run, and a clip's row does not depend on where the clip lies in the set or on the
+ * other rows.  The handle serves the error text only: its own parameters are not read.  Null pointers, misaligned pointers (8 bytes for
+ * doubles and offsets, 4 for the rest), n < 1 and a beta <= 0 give CVVDP_E_ARG before any launch.
+ *
+ * cvvdp_pool_dataset_loss: MSELoss of train.py:145 and its gradient, loss = (1/n) sum (jod - target)^2 to dev_loss[1] and
+ * (2/n) sum (jod - target) grad to dev_dloss[9], one workgroup, float64, the same fixed order over rows.
+ * Added; nothing else changed, so CVVDP_ABI_VERSION stays 14. */
+#define CVVDP_POOL_THETA_COUNT 9
+int cvvdp_pool_dataset(cvvdp_handle* h, const float* dev_q, const int64_t* dev_offset, const int32_t* dev_shape, const int32_t* dev_index,
+                       int32_t n, const double* dev_theta, const double beta[3], double* dev_jod, double* dev_grad, void* stream);
+int cvvdp_pool_dataset_loss(cvvdp_handle* h, const double* dev_jod, const double* dev_grad, const double* dev_target, int32_t n,
+                            double* dev_loss, double* dev_dloss, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
