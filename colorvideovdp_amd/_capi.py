@@ -137,6 +137,10 @@ class PreviewArgs(C.Structure):
 RGBE_E_MAGIC, RGBE_E_XYZE, RGBE_E_ORIENTATION, RGBE_E_SIZE, RGBE_E_BUFFER, RGBE_E_TRUNCATED, RGBE_E_RUN, RGBE_E_SCANLINE_WIDTH, RGBE_E_ZERO_COUNT = \
     range(-101, -110, -1)
 
+WRT = {"test": 1, "reference": 2, "both": 3}      # CVVDP_WRT_*
+# (handle, wrt, test, strides, reference, strides, grad, strides, bytes, grad_ref, strides, bytes, scratch, bytes, stream)
+_GRAD_WRT_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                  C.c_size_t, C.c_void_p, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
 SYMBOLS = {
     "cvvdp_abi_version": (C.c_int, []),
     "cvvdp_build_flags": (C.c_int, []),
@@ -195,6 +199,13 @@ SYMBOLS = {
     "cvvdp_video_gradient_blocks_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_video_gradient_block": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_image_gradient_wrt_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
+    "cvvdp_image_gradient_wrt": (C.c_int, _GRAD_WRT_ARGS),
+    "cvvdp_video_gradient_wrt_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
+    "cvvdp_video_gradient_wrt": (C.c_int, _GRAD_WRT_ARGS),
+    "cvvdp_video_gradient_blocks_wrt_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
+    "cvvdp_video_gradient_blocks_begin_wrt": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_video_gradient_block_wrt": (C.c_int, _GRAD_WRT_ARGS),
     "cvvdp_param_gradient_scratch_bytes": (C.c_size_t, [C.c_void_p]),
     "cvvdp_param_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_pool_dataset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double),

@@ -7,6 +7,9 @@
 //   4. the blur's adjoint on G, columns then rows                  -> t1   (same levels)
 //   5. min's routing (ties in half), contrast                      -> d = dJOD/d(layer), ey = dJOD/d(expanded Y)
 // then the baseband, then coarsest to finest the totals: direct + expand^T (finer level) + reduce^T (coarser total), and the display model.
+// The *_wrt entries ask for the gradient in the reference as well: steps 1 - 4 serve both sides and run once; step 5, the
+// baseband and the totals run per side, the reference's (k_grad_contrast_ref, k_grad_base_ref) on planes of its own, and the display model
+// is applied at the reference's samples.
 // Every kernel is a gather, one thread per output element, with no atomics: the same bits on every run.  The blur passes read their 13
 // (adjoint: up to 39) taps from global memory, which a level's three planes leave in L2; this pass has no performance target (tools/grad_bench.py).
 #include <new>
@@ -81,6 +84,21 @@ __global__ __launch_bounds__(GT) void k_grad_contrast(const GradBandArgsT<NC> a)
   a.ey[(int64_t)item * P + i] = ey;
 }
 
+// the reference side of the same step: a.d / a.ey are the REFERENCE's outputs (launch_chain swaps them in)
+template <int NC>
+__global__ __launch_bounds__(GT) void k_grad_contrast_ref(const GradBandArgsT<NC> a) {
+  GRAD_PIXEL(a.H, a.W);
+  const int item = blockIdx.y;
+  float gm[NC], dir[NC], d[NC], ey;
+  for (int c = 0; c < NC; ++c) {
+    gm[c] = a.t1[((int64_t)c * a.B + item) * P + i];
+    dir[c] = a.t2[((int64_t)c * a.B + item) * P + i];
+  }
+  g_band_contrast_ref(a, item, y, x, gm, dir, d, ey);
+  for (int c = 0; c < NC; ++c) a.d[((int64_t)c * a.B + item) * P + i] = d[c];
+  a.ey[(int64_t)item * P + i] = ey;
+}
+
 // One block per item (the band is at most a few hundred samples): the mean backgrounds, then per sample the direct part and its share
 // of dJOD/dLt, then the mean's own gradient to every test Y sample at or above the clamp
 template <int NC>
@@ -102,6 +120,34 @@ __global__ __launch_bounds__(256) void k_grad_base(const GradBaseArgsT<NC> a) {
   gL = block_sum(gL, s_tmp) / (float)P;
   for (int i = t; i < P; i += 256)          // (each thread revisits the samples it wrote itself)
     if (g[i] >= 0.01f) a.d[(int64_t)item * P + i] += gL;
+}
+
+// The reference side of the baseband: besides its own contrast, the mean reference background carries the sensitivity of every sample
+// (NC + 1 block sums, each in the fixed order of block_sum); a.d is the REFERENCE's output
+template <int NC>
+__global__ __launch_bounds__(256) void k_grad_base_ref(const GradBaseArgsT<NC> a) {
+  __shared__ float s_tmp[4];
+  const int item = blockIdx.x, t = threadIdx.x;
+  const int P = a.H * a.W;
+  const float* g = a.g + (int64_t)item * P;
+  float Lb[2];
+  base_bkg_mean<2>(g, a.gps, P, s_tmp, Lb);
+  float S[NC], dlnS[NC], gS[NC];
+  g_base_sens(a, Lb[1], S);
+  g_base_sens_slope(a, Lb[1], dlnS);
+  for (int c = 0; c < NC; ++c) gS[c] = 0.0f;
+  float gL = 0.0f;
+  for (int i = t; i < P; i += 256) {
+    float d[NC];
+    gL += g_base_pixel_ref(a, item, i, Lb[0], Lb[1], S, d, gS);
+    for (int c = 0; c < NC; ++c) a.d[((int64_t)c * a.B + item) * P + i] = d[c];
+  }
+  gL = block_sum(gL, s_tmp);
+  for (int c = 0; c < NC; ++c) gL += block_sum(gS[c], s_tmp) * S[c] * dlnS[c];
+  gL /= (float)P;
+  const float* gr = g + a.gps;               // the reference's Y plane
+  for (int i = t; i < P; i += 256)          // (each thread revisits the samples it wrote itself)
+    if (gr[i] >= 0.01f) a.d[(int64_t)item * P + i] += gL;
 }
 
 template <int NC>
@@ -143,6 +189,7 @@ void blur_pass(const float* in, float* out, int H, int W, int planes, bool verti
 template <int NC>
 void launch_chain(const GradChain<NC>& c, hipStream_t s) {
   const int L = c.L, B = c.items;
+  const bool test = c.wrt == 0 || (c.wrt & CVVDP_WRT_TEST), ref = c.wrt & CVVDP_WRT_REFERENCE;
   for (int l = 0; l + 1 < L; ++l) {
     const GradBandArgsT<NC>& a = c.band[l];
     const dim3 grid = pixel_grid(a.H, a.W, B);
@@ -156,10 +203,23 @@ void launch_chain(const GradChain<NC>& c, hipStream_t s) {
       blur_pass(a.t1, a.t0, a.H, a.W, NC * B, false, true, a.taps, s);
       blur_pass(a.t0, a.t1, a.H, a.W, NC * B, true, true, a.taps, s);
     }
-    hipLaunchKernelGGL(k_grad_contrast<NC>, grid, dim3(GT), 0, s, a);
+    if (test) hipLaunchKernelGGL(k_grad_contrast<NC>, grid, dim3(GT), 0, s, a);
+    if (ref) {
+      GradBandArgsT<NC> r = a;
+      r.d = c.ref[l].d; r.ey = c.ref[l].ey;
+      hipLaunchKernelGGL(k_grad_contrast_ref<NC>, grid, dim3(GT), 0, s, r);
+    }
   }
-  hipLaunchKernelGGL(k_grad_base<NC>, dim3(B), dim3(256), 0, s, c.base);
-  for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum<NC>, pixel_grid(c.acc[l].H, c.acc[l].W, B), dim3(GT), 0, s, c.acc[l]);
+  if (test) {
+    hipLaunchKernelGGL(k_grad_base<NC>, dim3(B), dim3(256), 0, s, c.base);
+    for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum<NC>, pixel_grid(c.acc[l].H, c.acc[l].W, B), dim3(GT), 0, s, c.acc[l]);
+  }
+  if (ref) {
+    GradBaseArgsT<NC> r = c.base;
+    r.d = c.ref[L - 1].d;
+    hipLaunchKernelGGL(k_grad_base_ref<NC>, dim3(B), dim3(256), 0, s, r);
+    for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum<NC>, pixel_grid(c.acc_r[l].H, c.acc_r[l].W, B), dim3(GT), 0, s, c.acc_r[l]);
+  }
 }
 
 }  // namespace
@@ -168,7 +228,8 @@ void launch_image_gradient(const GradPlan& p, hipStream_t s) {
   const int B = p.pool.B;
   hipLaunchKernelGGL(k_grad_pool, dim3((B + 63) / 64), dim3(64), 0, s, p.pool);
   launch_chain<3>(p.chain, s);
-  hipLaunchKernelGGL(k_grad_display, pixel_grid(p.dsp.H, p.dsp.W, B), dim3(GT), 0, s, p.dsp);
+  if (p.chain.wrt & CVVDP_WRT_TEST) hipLaunchKernelGGL(k_grad_display, pixel_grid(p.dsp.H, p.dsp.W, B), dim3(GT), 0, s, p.dsp);
+  if (p.chain.wrt & CVVDP_WRT_REFERENCE) hipLaunchKernelGGL(k_grad_display, pixel_grid(p.dsp_r.H, p.dsp_r.W, B), dim3(GT), 0, s, p.dsp_r);
 }
 
 void launch_grad_chain4(const GradChain<4>& c, hipStream_t s) { launch_chain<4>(c, s); }
@@ -192,6 +253,17 @@ int cvvdp_image_gradient(cvvdp_handle* h, const void* dev_test, const int64_t st
   return cvvdp::run_plan<cvvdp::GradPlan>(
       [&](auto& p) { return cvvdp::grad_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
       [&](auto& p) { cvvdp::launch_image_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_check_launch(h); });
+}
+
+size_t cvvdp_image_gradient_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt) { return cvvdp::grad_wrt_scratch(h, 0, wrt); }
+
+int cvvdp_image_gradient_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test, const int64_t strides_test[5], const void* dev_ref,
+                             const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
+                             const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
+  const cvvdp::GradSides sd{wrt, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_ref, strides_ref, dev_grad_ref, strides_grad_ref, grad_ref_bytes};
+  return cvvdp::run_plan<cvvdp::GradPlan>([&](auto& p) { return cvvdp::grad_prepare_wrt(h, sd, dev_scratch, scratch_bytes, p); },
+                                          [&](auto& p) { cvvdp::launch_image_gradient(p, static_cast<hipStream_t>(stream)); },
+                                          [&] { return cvvdp::grad_check_launch(h); });
 }
 
 }  // extern "C"

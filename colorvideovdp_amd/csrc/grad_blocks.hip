@@ -103,22 +103,31 @@ void launch_grad_blocks_begin(const GradBlocksPlan& p, hipStream_t s) {
     hipLaunchKernelGGL(k_blocks_fir_weights, dim3((unsigned)((n + VT - 1) / VT)), dim3(VT), 0, s, p.fw);
   }
   (void)hipMemsetAsync(p.fir.carry, 0, p.carry_floats * sizeof(float), s);
+  if (p.fir_r.carry) (void)hipMemsetAsync(p.fir_r.carry, 0, p.carry_floats * sizeof(float), s);      // (both sides: the reference's own carry)
 }
 
+namespace {
+// the streamed adjoint of one side
+void launch_fir_stream(bool slots, const GradFirStreamArgs& fir, hipStream_t s) {
+  const GradFirAdjArgs& f = fir.a;
+  const unsigned px = (unsigned)(((int64_t)f.H * f.W + VT - 1) / VT);
+  if (slots) {
+    hipLaunchKernelGGL(k_blocks_fir_slots, dim3(px, f.B), dim3(VT), 0, s, fir);
+  } else if (f.reg_wl == 9) {
+    hipLaunchKernelGGL(k_blocks_fir_reg<9>, dim3(px, f.B), dim3(VT), 0, s, fir);
+  } else if (f.reg_wl == 17) {
+    hipLaunchKernelGGL(k_blocks_fir_reg<17>, dim3(px, f.B), dim3(VT), 0, s, fir);
+  } else {
+    hipLaunchKernelGGL(k_blocks_fir_reg<CVVDP_GRAD_FIR_WL>, dim3(px, f.B), dim3(VT), 0, s, fir);
+  }
+}
+}  // namespace
+
 void launch_grad_blocks_block(const GradBlocksPlan& p, hipStream_t s) {
-  const GradFirAdjArgs& f = p.fir.a;
   hipLaunchKernelGGL(k_blocks_vpool_coef, dim3((unsigned)((p.chain.items + VT - 1) / VT)), dim3(VT), 0, s, p.pool);
   launch_grad_chain4(p.chain, s);
-  const unsigned px = (unsigned)(((int64_t)f.H * f.W + VT - 1) / VT);
-  if (p.slots) {
-    hipLaunchKernelGGL(k_blocks_fir_slots, dim3(px, f.B), dim3(VT), 0, s, p.fir);
-  } else if (f.reg_wl == 9) {
-    hipLaunchKernelGGL(k_blocks_fir_reg<9>, dim3(px, f.B), dim3(VT), 0, s, p.fir);
-  } else if (f.reg_wl == 17) {
-    hipLaunchKernelGGL(k_blocks_fir_reg<17>, dim3(px, f.B), dim3(VT), 0, s, p.fir);
-  } else {
-    hipLaunchKernelGGL(k_blocks_fir_reg<CVVDP_GRAD_FIR_WL>, dim3(px, f.B), dim3(VT), 0, s, p.fir);
-  }
+  if (p.chain.wrt & CVVDP_WRT_TEST) launch_fir_stream(p.slots, p.fir, s);
+  if (p.chain.wrt & CVVDP_WRT_REFERENCE) launch_fir_stream(p.slots, p.fir_r, s);
 }
 
 }  // namespace cvvdp
@@ -139,6 +148,23 @@ int cvvdp_video_gradient_block(cvvdp_handle* h, const void* dev_test, const int6
   return cvvdp::run_plan<cvvdp::GradBlocksPlan>(
       [&](auto& p) { return cvvdp::grad_blocks_block_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
       [&](auto& p) { cvvdp::launch_grad_blocks_block(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_blocks_check_launch(h, true); });
+}
+
+size_t cvvdp_video_gradient_blocks_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt) { return cvvdp::grad_wrt_scratch(h, 2, wrt); }
+
+int cvvdp_video_gradient_blocks_begin_wrt(cvvdp_handle* h, int32_t wrt, void* dev_scratch, size_t scratch_bytes, void* stream) {
+  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_begin_prepare_wrt(h, wrt, dev_scratch, scratch_bytes, p); },
+                                                [&](auto& p) { cvvdp::launch_grad_blocks_begin(p, static_cast<hipStream_t>(stream)); },
+                                                [&] { return cvvdp::grad_blocks_check_launch(h, false); });
+}
+
+int cvvdp_video_gradient_block_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test, const int64_t strides_test[5], const void* dev_ref,
+                                   const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
+                                   const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
+  const cvvdp::GradSides sd{wrt, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_ref, strides_ref, dev_grad_ref, strides_grad_ref, grad_ref_bytes};
+  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_block_prepare_wrt(h, sd, dev_scratch, scratch_bytes, p); },
+                                                [&](auto& p) { cvvdp::launch_grad_blocks_block(p, static_cast<hipStream_t>(stream)); },
+                                                [&] { return cvvdp::grad_blocks_check_launch(h, true); });
 }
 
 }  // extern "C"

@@ -131,11 +131,18 @@ struct GradPixelT {
   float Lt, exY;           // test background max(exY, 0.01) and the expanded test Y it comes from
 };
 using GradPixel = GradPixelT<3>;
+// what the reference side's gradient needs on top of that
+template <int NC>
+struct GradPixelRefT {
+  float layer[NC];         // reference Laplacian sample
+  float dlnS[NC];          // (dS_c / dLr) / S_c: the CSF look-up's slope in the reference background; 0 on a clamped index
+  float Lr, exY;           // reference background max(exY, 0.01) and the expanded reference Y it comes from
+};
 
 // NC = 4 (video): channel 3 is the transient one -- planes 6 / 7, CSF row 3, its own gain, mask exponent and cross-channel weights; its
 // contrast is divided by the sustained-Y background like the others
 template <int NC>
-GRAD_HD void g_band_pixel(const GradBandArgsT<NC>& a, int item, int y, int x, GradPixelT<NC>& o) {
+GRAD_HD void g_band_pixel(const GradBandArgsT<NC>& a, int item, int y, int x, GradPixelT<NC>& o, GradPixelRefT<NC>* ref = nullptr) {
   const int64_t P = (int64_t)a.H * a.W, Pc = (int64_t)a.Hc * a.Wc;
   const float* g = a.g + (int64_t)item * P + (int64_t)y * a.W + x;
   const float* gc = a.gc + (int64_t)item * Pc;
@@ -147,6 +154,8 @@ GRAD_HD void g_band_pixel(const GradBandArgsT<NC>& a, int item, int y, int x, Gr
   const float Lt = fmaxf(ext[0], 0.01f), Lr = fmaxf(exr[0], 0.01f);                  // lpyr_dec.py:394
   const float logL = g_log2(Lr) * kLog10_2;                                          // :408
   float ind = (logL - a.logL_first) * ((float)(CVVDP_CSF_NODES - 1) / (a.logL_last - a.logL_first));     // interp.py:93
+  // the clamp passes its gradient at the bound; at the last node i1 == i0 and the look-up no longer depends on the index
+  const float dind = (ind >= 0.0f && ind < (float)(CVVDP_CSF_NODES - 1)) ? ((float)(CVVDP_CSF_NODES - 1) / (a.logL_last - a.logL_first)) / Lr : 0.0f;
   ind = fminf(fmaxf(ind, 0.0f), (float)(CVVDP_CSF_NODES - 1));
   const int i0 = (int)ind, i1 = g_min(i0 + 1, CVVDP_CSF_NODES - 1);
   const float fr = ind - (float)i0;
@@ -158,7 +167,9 @@ GRAD_HD void g_band_pixel(const GradBandArgsT<NC>& a, int item, int y, int x, Gr
     o.S[c] = S; o.layer[c] = lt;
     o.Tp[c] = fminf(lt / Lt, 1000.0f) * a.band_mul * S;                                         // lpyr_dec.py:402, :66
     o.Rp[c] = fminf(lr / Lr, 1000.0f) * a.band_mul * S;
+    if (ref) { ref->layer[c] = lr; ref->dlnS[c] = (l1 - l0) * dind; }
   }
+  if (ref) { ref->Lr = Lr; ref->exY = exr[0]; }
 }
 
 // pass 1: m = min(|T'|, |R'|) (cvvdp_metric.py:845)
@@ -222,6 +233,29 @@ GRAD_HD void g_band_contrast(const GradBandArgsT<NC>& a, int item, int y, int x,
   ey = (px.exY >= 0.01f ? gL : 0.0f) - d[0];                                          // clamp(min = 0.01) passes at the bound
 }
 
+// pass 5 for the REFERENCE: d[c] = dJOD/d(reference layer_c), ey = dJOD/d(expanded reference Y); the expanded chroma planes receive -d[c].
+// The reference's background divides its own contrast and, through the CSF look-up, sets the sensitivity S of T' and R' alike.
+template <int NC>
+GRAD_HD void g_band_contrast_ref(const GradBandArgsT<NC>& a, int item, int y, int x, const float (&gm)[NC], const float (&dir)[NC], float (&d)[NC],
+                                 float& ey) {
+  GradPixelT<NC> px;
+  GradPixelRefT<NC> rf;
+  g_band_pixel(a, item, y, x, px, &rf);
+  float gL = 0.0f;
+  for (int c = 0; c < NC; ++c) {
+    const float at = fabsf(px.Tp[c]), ar = fabsf(px.Rp[c]);
+    const float w = at < ar ? 1.0f : (at == ar ? 0.5f : 0.0f);                        // the test side's tie rule
+    const float gTp = dir[c] + gm[c] * w * g_sign(px.Tp[c]);
+    const float gRp = -dir[c] + gm[c] * (1.0f - w) * g_sign(px.Rp[c]);
+    const float ratio = rf.layer[c] / rf.Lr;
+    const float gx = ratio <= 1000.0f ? gRp * px.S[c] * a.band_mul : 0.0f;
+    d[c] = gx / rf.Lr;
+    gL -= gx * rf.layer[c] / (rf.Lr * rf.Lr);
+    gL += (gTp * px.Tp[c] + gRp * px.Rp[c]) * rf.dlnS[c];                            // gS dS/dLr, gS = (gT' T' + gR' R') / S
+  }
+  ey = (rf.exY >= 0.01f ? gL : 0.0f) - d[0];
+}
+
 // ---------------------------------------------------------------- baseband (lpyr_dec.py:378-384, cvvdp_metric.py:711-712)
 // sensitivities at the reference's mean background Lr (k_baseband's expressions)
 template <int NC>
@@ -249,6 +283,36 @@ GRAD_HD float g_base_pixel(const GradBaseArgsT<NC>& a, int item, int i, float Lt
     gL -= gx * gt / (Lt * Lt);
   }
   return gL;
+}
+
+// the REFERENCE side of a sample: d[c] = dJOD/dg_r[c] without the part through the mean background; returns this sample's share of
+// dJOD/dLr through the contrast and adds to gS[c] its share of dJOD/dS_c (= gD |diff|)
+template <int NC>
+GRAD_HD float g_base_pixel_ref(const GradBaseArgsT<NC>& a, int item, int i, float Lt, float Lr, const float (&S)[NC], float (&d)[NC], float (&gS)[NC]) {
+  const int64_t P = (int64_t)a.H * a.W;
+  const float* g = a.g + (int64_t)item * P + i;
+  float gL = 0.0f;
+  for (int c = 0; c < NC; ++c) {
+    const float gt = g[(2 * c) * a.gps], gr = g[(2 * c + 1) * a.gps];
+    const float rr = gr / Lr;
+    const float diff = fminf(gt / Lt, 1000.0f) - fminf(rr, 1000.0f);
+    const float D = fabsf(diff) * S[c];
+    const float gD = a.coef[((int64_t)item * NC + c) * a.L + a.level] * (D + kEps);
+    const float gx = rr <= 1000.0f ? -gD * S[c] * g_sign(diff) : 0.0f;
+    d[c] = gx / Lr;
+    gL -= gx * gr / (Lr * Lr);
+    gS[c] += gD * fabsf(diff);
+  }
+  return gL;
+}
+// (dS_c / dLr) / S_c of g_base_sens at the mean reference background
+template <int NC>
+GRAD_HD void g_base_sens_slope(const GradBaseArgsT<NC>& a, float Lr, float (&dlnS)[NC]) {
+  const float ind = (log10f(Lr) - a.logL_first) / (a.logL_last - a.logL_first) * (float)(CVVDP_CSF_NODES - 1);
+  const float dind = (ind >= 0.0f && ind < (float)(CVVDP_CSF_NODES - 1)) ? ((float)(CVVDP_CSF_NODES - 1) / (a.logL_last - a.logL_first)) / Lr : 0.0f;
+  const float cl = fminf(fmaxf(ind, 0.0f), (float)(CVVDP_CSF_NODES - 1));
+  const int i0 = (int)cl, i1 = g_min(i0 + 1, CVVDP_CSF_NODES - 1);
+  for (int c = 0; c < NC; ++c) dlnS[c] = (a.lut[c * CVVDP_CSF_NODES + i1] - a.lut[c * CVVDP_CSF_NODES + i0]) * dind;
 }
 
 // ---------------------------------------------------------------- dJOD/dQ_per_ch in closed form (cvvdp_metric.py:610-658), float64

@@ -106,14 +106,11 @@ __global__ __launch_bounds__(VT) void k_grad_fir_gather(const GradFirAdjArgs a) 
 
 }  // namespace
 
-void launch_video_gradient(const GradVideoPlan& p, hipStream_t s) {
-  const GradFirAdjArgs& f = p.fir;
-  hipLaunchKernelGGL(k_grad_vpool, dim3(p.pool.B), dim3(VT), 0, s, p.pool);
-  launch_grad_chain4(p.chain, s);
+namespace {
+// the FIR-plus-display adjoint of one side (the gather variant's table is written before the first)
+void launch_fir_adj(const GradFirAdjArgs& f, hipStream_t s) {
   const unsigned px = (unsigned)(((int64_t)f.H * f.W + VT - 1) / VT);
   if (f.reg_wl == 0) {
-    const int64_t n = (int64_t)4 * f.F * f.F;
-    hipLaunchKernelGGL(k_grad_fir_weights, dim3((unsigned)((n + VT - 1) / VT)), dim3(VT), 0, s, p.fw);
     hipLaunchKernelGGL(k_grad_fir_gather, dim3(px, f.F, f.B), dim3(VT), 0, s, f);
   } else if (f.reg_wl == 9) {
     hipLaunchKernelGGL(k_grad_fir_adj<9>, dim3(px, f.B), dim3(VT), 0, s, f);
@@ -122,6 +119,20 @@ void launch_video_gradient(const GradVideoPlan& p, hipStream_t s) {
   } else {
     hipLaunchKernelGGL(k_grad_fir_adj<CVVDP_GRAD_FIR_WL>, dim3(px, f.B), dim3(VT), 0, s, f);
   }
+}
+}  // namespace
+
+void launch_video_gradient(const GradVideoPlan& p, hipStream_t s) {
+  const bool ref = p.chain.wrt & CVVDP_WRT_REFERENCE, test = !ref || (p.chain.wrt & CVVDP_WRT_TEST);
+  const GradFirAdjArgs& f = test ? p.fir : p.fir_r;
+  hipLaunchKernelGGL(k_grad_vpool, dim3(p.pool.B), dim3(VT), 0, s, p.pool);
+  launch_grad_chain4(p.chain, s);
+  if (f.reg_wl == 0) {
+    const int64_t n = (int64_t)4 * f.F * f.F;
+    hipLaunchKernelGGL(k_grad_fir_weights, dim3((unsigned)((n + VT - 1) / VT)), dim3(VT), 0, s, p.fw);
+  }
+  if (test) launch_fir_adj(p.fir, s);
+  if (ref) launch_fir_adj(p.fir_r, s);
 }
 
 }  // namespace cvvdp
@@ -136,6 +147,17 @@ int cvvdp_video_gradient(cvvdp_handle* h, const void* dev_test, const int64_t st
   return cvvdp::run_plan<cvvdp::GradVideoPlan>(
       [&](auto& p) { return cvvdp::grad_video_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
       [&](auto& p) { cvvdp::launch_video_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_video_check_launch(h); });
+}
+
+size_t cvvdp_video_gradient_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt) { return cvvdp::grad_wrt_scratch(h, 1, wrt); }
+
+int cvvdp_video_gradient_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test, const int64_t strides_test[5], const void* dev_ref,
+                             const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
+                             const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
+  const cvvdp::GradSides sd{wrt, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_ref, strides_ref, dev_grad_ref, strides_grad_ref, grad_ref_bytes};
+  return cvvdp::run_plan<cvvdp::GradVideoPlan>([&](auto& p) { return cvvdp::grad_video_prepare_wrt(h, sd, dev_scratch, scratch_bytes, p); },
+                                               [&](auto& p) { cvvdp::launch_video_gradient(p, static_cast<hipStream_t>(stream)); },
+                                               [&] { return cvvdp::grad_video_check_launch(h); });
 }
 
 }  // extern "C"

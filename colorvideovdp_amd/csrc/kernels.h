@@ -656,17 +656,31 @@ struct GradDisplayArgs {     // total of level 0 -> dJOD/dV, written through the
   int32_t H, W, B;
   DisplayArgs dm;
 };
+// Which side(s) a pixel gradient is asked for (cvvdp_hip.h CVVDP_WRT_*).  The steps of a level up to the blur's adjoint
+// are shared; the contrast step, the baseband and the pyramid adjoints run once per side, the reference's on outputs of its own.
+struct GradRefOut { float* d; float* ey; };  // the reference side's d / ey of one level (band[l].d / .ey are the test side's)
 template <int NC>
 struct GradChain {           // the band chain of every gradient plan: levels finest first, the baseband, the totals coarsest first
   int32_t L, items;
   GradBandArgsT<NC> band[CVVDP_MAX_LEVELS];  // levels 0 .. L - 2
   GradBaseArgsT<NC> base;
   GradAccumArgs acc[CVVDP_MAX_LEVELS];       // (left empty by the parameter gradient, which stops before the pyramid adjoints)
+  int32_t wrt;                               // CVVDP_WRT_*; 0 (a plan that knows no sides) is CVVDP_WRT_TEST
+  GradRefOut ref[CVVDP_MAX_LEVELS];          // wrt includes the reference: its outputs per level (ey: all but the last) ...
+  GradAccumArgs acc_r[CVVDP_MAX_LEVELS];     // ... and its pyramid adjoints
 };
 struct GradPlan {            // everything cvvdp_image_gradient launches, filled by core.cpp
   GradPoolArgs pool;
   GradChain<3> chain;
   GradDisplayArgs dsp;
+  GradDisplayArgs dsp_r;     // the reference side: its total of level 0, the reference tensor, its gradient
+};
+// The two sides of a pixel-gradient call: tensor, its strides (B, C, F, H, W in elements), gradient buffer, its strides and bytes.  A
+// side wrt does not include is not looked at.
+struct GradSides {
+  int32_t wrt;
+  const void* test; const int64_t* st; float* grad; const int64_t* sg; size_t grad_bytes;
+  const void* ref; const int64_t* sr; float* grad_r; const int64_t* sgr; size_t grad_r_bytes;
 };
 // A C ABI entry of the gradient routes: the plan (tens of kilobytes: not on the stack), filled by prepare(plan); then launch(plan) and
 // what check() says of the launches
@@ -683,6 +697,9 @@ static_assert(sizeof(GradBandArgsT<4>) <= 4096 && sizeof(GradDisplayArgs) <= 409
 size_t grad_scratch(const cvvdp_handle* h);
 int grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
                  size_t scratch_bytes, GradPlan& plan);
+// the same for the *_wrt entries, all routes (route: 0 image, 1 one-block video, 2 blocks); an unknown wrt has no size and is refused
+size_t grad_wrt_scratch(const cvvdp_handle* h, int route, int32_t wrt);
+int grad_prepare_wrt(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradPlan& plan);
 int grad_check_launch(cvvdp_handle* h);
 void launch_image_gradient(const GradPlan& p, hipStream_t s);
 
@@ -719,11 +736,13 @@ struct GradVideoPlan {       // everything cvvdp_video_gradient launches, filled
   GradChain<4> chain;
   GradFirWeightArgs fw;
   GradFirAdjArgs fir;
+  GradFirAdjArgs fir_r;      // the reference side: its G, the reference tensor, its gradient
 };
 static_assert(sizeof(GradFirAdjArgs) <= 4096 && sizeof(GradFirWeightArgs) <= 4096, "kernel arguments of the video gradient kernels");
 size_t grad_video_scratch(const cvvdp_handle* h);
 int grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
                        size_t scratch_bytes, GradVideoPlan& plan);
+int grad_video_prepare_wrt(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradVideoPlan& plan);
 int grad_video_check_launch(cvvdp_handle* h);
 // grad.hip: the band chain (levels, baseband, pyramid adjoints) for 4 channels; grad_video.hip: pooling and the FIR / display adjoint
 void launch_grad_chain4(const GradChain<4>& c, hipStream_t s);
@@ -752,12 +771,15 @@ struct GradBlocksPlan {      // everything cvvdp_video_gradient_blocks_begin / _
   GradFirWeightArgs fw;     // fw.wt = padw
   GradFirStreamArgs fir;
   size_t carry_floats;
+  GradFirStreamArgs fir_r;  // the reference side, with a carry of its own (carry_floats as well)
 };
 static_assert(sizeof(GradFirStreamArgs) <= 4096, "kernel arguments of the streamed FIR adjoint");
 size_t grad_blocks_scratch(const cvvdp_handle* h);
 int grad_blocks_begin_prepare(cvvdp_handle* h, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
 int grad_blocks_block_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
                               size_t scratch_bytes, GradBlocksPlan& plan);
+int grad_blocks_begin_prepare_wrt(cvvdp_handle* h, int32_t wrt, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
+int grad_blocks_block_prepare_wrt(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
 int grad_blocks_check_launch(cvvdp_handle* h, bool block);      // ... and, after a block's launches, moves the handle on to the next block
 void launch_grad_blocks_begin(const GradBlocksPlan& p, hipStream_t s);
 void launch_grad_blocks_block(const GradBlocksPlan& p, hipStream_t s);

@@ -269,17 +269,20 @@ class _JodLoss(torch.autograd.Function):
     """10 - JOD with the gradient of cvvdp.predict_with_gradient (cvvdp.differentiable_loss)."""
 
     @staticmethod
-    def forward(ctx, test, reference, metric, dim_order, frames_per_second, block_frames=None):
-        jod, grad = metric.predict_with_gradient(test, reference, dim_order, frames_per_second, block_frames=block_frames)
-        ctx.save_for_backward(grad)
-        ctx.batch_shape = [n if ch == "B" else 1 for ch, n in zip(dim_order.upper(), grad.shape)]
+    def forward(ctx, test, reference, metric, dim_order, frames_per_second, block_frames=None, wrt="test"):
+        jod, grad = metric.predict_with_gradient(test, reference, dim_order, frames_per_second, block_frames=block_frames, wrt=wrt)
+        grads = grad if wrt == "both" else (grad,)
+        ctx.save_for_backward(*grads)
+        ctx.wrt = wrt
+        ctx.batch_shape = [n if ch == "B" else 1 for ch, n in zip(dim_order.upper(), grads[0].shape)]
         return 10.0 - jod
 
     @staticmethod
     def backward(ctx, upstream):
-        grad, = ctx.saved_tensors
         up = upstream if upstream.dim() == 0 else upstream.reshape(ctx.batch_shape)      # one factor per batch item
-        return -grad * up, None, None, None, None, None
+        out = [-g * up for g in ctx.saved_tensors]
+        g_test, g_ref = {"test": (out[0], None), "reference": (None, out[0])}.get(ctx.wrt) or out
+        return g_test, g_ref, None, None, None, None, None
 
 
 _CSF_TABLES = {}
@@ -625,8 +628,10 @@ class cvvdp(vq_metric):
         Q_jod, _ = self.predict(test_cont, reference_cont, dim_order=dim_order, frames_per_second=frames_per_second)
         return 10.0 - Q_jod
 
-    def _gradient_inputs(self, test, reference, dim_order, frames_per_second=0, block_frames=None):
+    def _gradient_inputs(self, test, reference, dim_order, frames_per_second=0, block_frames=None, wrt="test"):
         """What predict_with_gradient refuses, checked before anything touches the device; returns the BCFHW views."""
+        if not isinstance(wrt, str) or wrt not in _capi.WRT:
+            raise vq_exception(f'predict_with_gradient: wrt must be "test", "reference" or "both", not {wrt!r}')
         if block_frames is not None and block_frames != "auto":
             if isinstance(block_frames, bool) or not isinstance(block_frames, (int, np.integer)) or block_frames < 1:
                 raise vq_exception(f'predict_with_gradient: block_frames must be None, "auto" or an integer >= 1, not {block_frames!r}')
@@ -662,6 +667,9 @@ class cvvdp(vq_metric):
             raise vq_exception("predict_with_gradient: 1-channel content is out of scope, the images must have three colour channels")
         if tuple(t.shape[3:]) != tuple(r.shape[3:]) or (r.shape[0] != t.shape[0] and r.shape[0] != 1):
             raise vq_exception("predict_with_gradient: the reference must have the test's shape (or a batch of 1)")
+        if wrt != "test" and r.shape[0] != t.shape[0]:
+            raise vq_exception(f"predict_with_gradient: a reference of batch 1 against a test batch of {t.shape[0]} is refused with wrt = {wrt!r}: "
+                               "the gradient of the broadcast would be a sum over the items (expand the reference to the test's batch)")
         eotf, _ = self.display_photometry.eotf_params()
         if eotf in (1, 2):      # CVVDP_EOTF_PQ, CVVDP_EOTF_HLG
             raise vq_exception("predict_with_gradient: PQ and HLG displays are refused (the reference's own gradient is NaN as soon as a sample is 0)")
@@ -671,7 +679,7 @@ class cvvdp(vq_metric):
             raise vq_exception(f"predict_with_gradient: test and reference must be tensors on {self.device}")
         return t, r
 
-    def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None):
+    def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None, wrt="test"):
         """(jod, grad) of an image or of a short clip: `jod` as predict() returns it, `grad` = d jod / d test, float32 on the device, with
         the shape of `test` in the caller's dim_order; for a batch, grad[b] is the gradient of jod[b] (items do not interact).  float32
         tensors on the metric's device, three channels; sRGB, numeric-gamma and linear displays.  1-channel content, other dtypes, heat
@@ -694,16 +702,22 @@ class cvvdp(vq_metric):
         of one block once.  Workspace and scratch then grow with N, not with the clip: about 118 bytes per pixel and batch item x N, plus
         12 bytes x filter_len for what a block border cuts; only `grad` has the clip's size.  N + filter_len - 1 must not exceed
         CVVDP_MAX_WINDOW.  block_frames = "auto" takes the largest N the window limit and the free memory allow.  Images ignore it.
+        wrt = "reference" returns (jod, grad_reference), d jod / d reference with the shape of `reference`; wrt = "both" returns
+        (jod, (grad_test, grad_reference)).  Every route above takes it (the *_wrt entries); jod and grad_test are the bits of
+        wrt = "test", grad_reference the same bits for "reference" and "both" and, in blocks, for every N.  "both" runs the steps the two
+        sides share once and needs a second set of per-level planes: about 79 bytes per pixel and item for an image, 101 per pixel, frame
+        and item for a clip.  The refusals hold for both tensors; a reference of batch 1 against a larger test batch is refused as well.
         Out of scope: file sources, .yuv, --temp-resample, frame sharding."""
-        t, r = self._gradient_inputs(test, reference, dim_order, frames_per_second, block_frames)
+        t, r = self._gradient_inputs(test, reference, dim_order, frames_per_second, block_frames, wrt)
+        sides = (test, t, reference, r, wrt)
         if t.shape[2] > 1:
             if block_frames is not None:
-                return self._predict_video_with_gradient_blocks(test, t, r, dim_order, frames_per_second, block_frames)
-            return self._predict_video_with_gradient(test, t, r, dim_order, frames_per_second)
+                return self._predict_video_with_gradient_blocks(sides, dim_order, frames_per_second, block_frames)
+            return self._predict_video_with_gradient(sides, dim_order, frames_per_second)
         vs = video_source_array(t, r, 0, dim_order="BCFHW", display_photometry=self.display_photometry)
         Q, _, _ = self._score_range(vs, 0, 1)
         jod = self.do_pooling_and_jods(Q)
-        grad, _, call = self._pixel_gradient_entry("cvvdp_image_gradient", _capi.lib().cvvdp_image_gradient_scratch_bytes, test, t, dim_order)
+        grad, _, call = self._pixel_gradient_entry("cvvdp_image_gradient", "cvvdp_image_gradient_scratch_bytes", sides, dim_order)
         call()
         return jod.squeeze(), grad
 
@@ -731,36 +745,60 @@ class cvvdp(vq_metric):
                 setattr(self, k, v)
             self._block_hook = None
 
-    def _pixel_gradient_entry(self, name, scratch_bytes, test, t, dim_order, guard=None):
-        """Everything between the forward and the C entry `name` of a pixel gradient; t is the BCFHW view of test on the device.  Returns
-        grad, float32 with the shape of `test`; the scratch of scratch_bytes(handle) bytes, allocated under `guard` (stream-ordered: the
-        caching allocator may hand it out again once the kernels are queued); and call(stream=None), which runs the entry on the stream
-        (None: torch's current one) and checks it."""
-        grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
-        gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
-        assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
-        with guard or contextlib.nullcontext():
-            scratch = torch.empty(max(int(scratch_bytes(self._handle)), 16), dtype=torch.uint8, device=self.device)
-        st = (ctypes.c_int64 * 5)(*t.stride())
-        sg = (ctypes.c_int64 * 5)(*gv.stride())
-        entry = getattr(_capi.lib(), name)
+    def _pixel_gradient_entry(self, name, scratch_name, sides, dim_order, guard=None):
+        """Everything between the forward and the C entry `name` of a pixel gradient; sides = (test, t, reference, r, wrt), t and r the
+        BCFHW views on the device.  wrt = "test" calls `name` itself, the other two its sibling `name`_wrt.  Returns what
+        predict_with_gradient returns for this wrt: grad, float32 with the shape of `test` (of `reference`; the pair of them); the scratch
+        of as many bytes as the entry `scratch_name` answers, allocated under `guard` (stream-ordered: the caching allocator may hand it
+        out again once the kernels are queued); and call(stream=None), which runs the entry on the stream (None: torch's current one) and checks it."""
+        test, t, reference, r, wrt = sides
+        lib = _capi.lib()
 
-        def call(stream=None):
+        def side(tensor, view):
+            grad = torch.empty(tensor.shape, dtype=torch.float32, device=self.device)
+            gv = reshuffle_dims(grad, dim_order, "BCFHW")        # a view: the kernel writes the caller's layout through its strides
+            assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
+            return grad, (view.data_ptr(), (ctypes.c_int64 * 5)(*view.stride())), (gv.data_ptr(), (ctypes.c_int64 * 5)(*gv.stride()), grad.numel() * 4)
+
+        if wrt == "test":
+            grad, (pt, st), g_args = side(test, t)
+            with guard or contextlib.nullcontext():
+                scratch = torch.empty(max(int(getattr(lib, scratch_name)(self._handle)), 16), dtype=torch.uint8, device=self.device)
+            entry = getattr(lib, name)
+
+            def call(stream=None):
+                stream = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+                rc = entry(self._handle, pt, st, *g_args, scratch.data_ptr(), scratch.numel(), stream)
+                _capi.check(self._handle, rc, name)
+
+            return grad, scratch, call
+
+        name, code = name + "_wrt", _capi.WRT[wrt]
+        none = (None, None), (None, None, 0)
+        grad_t, v_t, g_t = side(test, t) if wrt == "both" else (None,) + none
+        grad_r, v_r, g_r = side(reference, r)
+        with guard or contextlib.nullcontext():
+            scratch = torch.empty(max(int(getattr(lib, scratch_name.replace("_scratch_bytes", "_wrt_scratch_bytes"))(self._handle, code)), 16),
+                                  dtype=torch.uint8, device=self.device)
+        entry = getattr(lib, name)
+
+        def call_wrt(stream=None):
             stream = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
-            rc = entry(self._handle, t.data_ptr(), st, gv.data_ptr(), sg, grad.numel() * 4, scratch.data_ptr(), scratch.numel(), stream)
+            rc = entry(self._handle, code, *v_t, *v_r, *g_t, *g_r, scratch.data_ptr(), scratch.numel(), stream)
             _capi.check(self._handle, rc, name)
 
-        return grad, scratch, call
+        return (grad_t, grad_r) if wrt == "both" else grad_r, scratch, call_wrt
 
-    def _predict_video_with_gradient(self, test, t, r, dim_order, frames_per_second):
-        """predict_with_gradient for a clip: t, r are the BCFHW views on the device."""
+    def _predict_video_with_gradient(self, sides, dim_order, frames_per_second):
+        """predict_with_gradient for a clip: sides = (test, t, reference, r, wrt); t, r are the BCFHW views on the device."""
+        _, t, _, r, wrt = sides
         if self._shard is not None:
             raise vq_exception("predict_with_gradient: not available with frame sharding")
         lib = _capi.lib()
         n_frames = int(t.shape[2])
 
         def text():
-            ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_scratch_bytes(self._handle))
+            ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_wrt_scratch_bytes(self._handle, _capi.WRT[wrt]))
             return (f"predict_with_gradient: the clip needs a workspace of {ws} bytes and a scratch of {sc} bytes as one temporal block, "
                     "which cannot be allocated on this device")
 
@@ -769,35 +807,40 @@ class cvvdp(vq_metric):
             vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
             with no_memory(text):
                 Q, _, _ = self._score_range(vs, 0, n_frames)
-            grad, _, call = self._pixel_gradient_entry("cvvdp_video_gradient", lib.cvvdp_video_gradient_scratch_bytes, test, t, dim_order, no_memory(text))
+            grad, _, call = self._pixel_gradient_entry("cvvdp_video_gradient", "cvvdp_video_gradient_scratch_bytes", sides, dim_order, no_memory(text))
             jod = self.do_pooling_and_jods(Q)       # (reads Q back: after the allocations, which then overlap the forward)
             call()
         return jod.squeeze(), grad
 
-    def _predict_video_with_gradient_blocks(self, test, t, r, dim_order, frames_per_second, block_frames):
-        """predict_with_gradient for a clip in temporal blocks: t, r are the BCFHW views on the device.  Pass 1 scores all blocks; the
+    def _predict_video_with_gradient_blocks(self, sides, dim_order, frames_per_second, block_frames):
+        """predict_with_gradient for a clip in temporal blocks: sides = (test, t, reference, r, wrt).  Pass 1 scores all blocks; the
         pooling terms of all frames are added on the device; pass 2 runs the same blocks again, the backward of a block after each."""
         if self._shard is not None:
             raise vq_exception("predict_with_gradient: not available with frame sharding")
         lib = _capi.lib()
+        _, t, _, r, wrt = sides
         n_frames = int(t.shape[2])
 
         def text():
-            ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_blocks_scratch_bytes(self._handle))
+            ws, sc = int(lib.cvvdp_workspace_bytes(self._handle)), int(lib.cvvdp_video_gradient_blocks_wrt_scratch_bytes(self._handle, _capi.WRT[wrt]))
             return (f"predict_with_gradient: blocks of {self.last_block_frames} frames need a workspace of {ws} bytes and a scratch of "
                     f"{sc} bytes, which cannot be allocated on this device")
 
-        # (_pixel_grad_plan: _pick_block_frames counts the backward's scratch when it sizes the blocks itself)
-        with self._borrowed(fuse_mode=2, block_frames=None if block_frames == "auto" else min(int(block_frames), n_frames), _pixel_grad_plan=True) as no_memory:
+        # (_pixel_grad_plan: _pick_block_frames counts the backward's scratch when it sizes the blocks itself; 2: the outputs and carry of both sides)
+        with self._borrowed(fuse_mode=2, block_frames=None if block_frames == "auto" else min(int(block_frames), n_frames),
+                            _pixel_grad_plan=2 if wrt == "both" else True) as no_memory:
             vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
             with no_memory(text):
                 Q, _, _ = self._score_range(vs, 0, n_frames)                   # pass 1: the normal block loop
                 self.block_frames = int(self.last_block_frames)                # (pass 2 walks the same blocks, whatever is free by then)
-            grad, scratch, after_block = self._pixel_gradient_entry("cvvdp_video_gradient_block", lib.cvvdp_video_gradient_blocks_scratch_bytes, test, t,
+            grad, scratch, after_block = self._pixel_gradient_entry("cvvdp_video_gradient_block", "cvvdp_video_gradient_blocks_scratch_bytes", sides,
                                                                     dim_order, no_memory(text))
             jod = self.do_pooling_and_jods(Q)       # (reads Q back: after the allocations, which then overlap the forward)
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = lib.cvvdp_video_gradient_blocks_begin(self._handle, scratch.data_ptr(), scratch.numel(), stream)
+            if wrt == "test":
+                rc = lib.cvvdp_video_gradient_blocks_begin(self._handle, scratch.data_ptr(), scratch.numel(), stream)
+            else:
+                rc = lib.cvvdp_video_gradient_blocks_begin_wrt(self._handle, _capi.WRT[wrt], scratch.data_ptr(), scratch.numel(), stream)
             _capi.check(self._handle, rc, "cvvdp_video_gradient_blocks_begin")
             if n_frames <= int(self.last_block_frames):
                 after_block(stream)                                             # one block: its pyramid is still in the workspace
@@ -806,15 +849,16 @@ class cvvdp(vq_metric):
                 self._score_range(vs, 0, n_frames)
         return jod.squeeze(), grad
 
-    def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None):
+    def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None, wrt="test"):
         """10 - JOD of an image or a short clip as a tensor attached to autograd (the reference's loss(): examples/ex_image_reconstruction.py
         runs with this method's name in place of `loss`).  backward() multiplies the gradient predict_with_gradient() stored by the
         upstream gradient, one factor per batch item; the reference receives None, and a reference that requires a gradient is refused.
         Clips: see predict_with_gradient; block_frames (None, an integer or "auto") is handed on to it, so that a clip of any length can
-        serve as a loss."""
-        if torch.is_tensor(reference) and reference.requires_grad:
-            raise vq_exception("differentiable_loss: a gradient for the reference is out of scope")
-        return _JodLoss.apply(test, reference, self, dim_order, frames_per_second, block_frames)
+        serve as a loss.  wrt = "reference" or "both" sends the reference its gradient as well (the test then receives one only with
+        "both"); with the default a reference that requires a gradient stays refused."""
+        if wrt == "test" and torch.is_tensor(reference) and reference.requires_grad:
+            raise vq_exception('differentiable_loss: a gradient for the reference is out of scope with wrt = "test" (wrt = "reference" or "both" gives it)')
+        return _JodLoss.apply(test, reference, self, dim_order, frames_per_second, block_frames, wrt)
 
     # ------------------------------------------------------------------ gradient in the model's parameters (calibration)
     @staticmethod
@@ -1081,8 +1125,9 @@ class cvvdp(vq_metric):
             fixed = pix * batch * 24 * (fl - 1)
             if getattr(self, "_pixel_grad_plan", False):
                 # cvvdp_video_gradient_block's scratch: three temporaries of 4 planes, 4 + 1 planes per pyramid level; the carry of fl slots
-                per_frame += pix * batch * (3 * 4 * 4 + 5 * 4 * 1.34)
-                fixed += pix * batch * 12 * fl
+                sides = int(self._pixel_grad_plan)      # (2: wrt = "both", a second set of outputs and a second carry)
+                per_frame += pix * batch * (3 * 4 * 4 + sides * 5 * 4 * 1.34)
+                fixed += pix * batch * 12 * fl * sides
             nb = int((budget - fixed) // per_frame)
             # heat maps leave the GPU over PCIe (2-6 B/pixel): 16-frame blocks let the copy of a block overlap the
             # kernels of the next one (4K supra-threshold, 64 frames: 111 ms as one block, 81 ms in blocks of 16)
@@ -1231,7 +1276,7 @@ class cvvdp(vq_metric):
         height, width, is_image, prefiltered = rt.height, rt.width, rt.is_image, rt.prefiltered
         key = (height, width, rt.n_total, first, count, rt.B, rt.C, is_image, None if is_image else float(vs.get_frames_per_second()), self.heatmap,
                bool(self.debug_dump or self.dump_channels is not None), int(self.fuse_mode), int(self.band_layout), self.score_frames, self._sink_on_device, self.block_frames, self.gpu_mem, float(self.pix_per_deg), self._cfg_version, prefiltered, getattr(self, "_feature_out", None) is not None,
-               self._host_resident(vs), bool(getattr(self, "_param_grad_plan", False)), bool(getattr(self, "_pixel_grad_plan", False)))
+               self._host_resident(vs), bool(getattr(self, "_param_grad_plan", False)), int(getattr(self, "_pixel_grad_plan", False)))
         cached = getattr(self, "_clip_cache", None)
         if cached is not None and cached[0] == key:
             clip, fl, F = cached[1], cached[2], cached[3]

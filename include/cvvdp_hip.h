@@ -542,6 +542,38 @@ int cvvdp_video_gradient_blocks_begin(cvvdp_handle* h, void* dev_scratch, size_t
 int cvvdp_video_gradient_block(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                                size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* The same three gradients in the test, in the REFERENCE, or in both: d JOD[b] / d reference[b] written to dev_grad_ref as dev_grad is.
+ * State, displays, refusals, their order and the conventions are those of the entry each one is the sibling of; wrt = CVVDP_WRT_TEST
+ * launches what that entry launches and gives its bits.  A side wrt does not include is not looked at (its pointers may be null); the
+ * null, alignment, extent and negative-stride checks apply to every side it includes.  Any other wrt is CVVDP_E_ARG, and so is a
+ * reference with a batch stride of 0 against a batch above 1 (a broadcast reference: its gradient would be a sum over the items).
+ *   dev_ref, strides_ref        the float32 reference the forward was scored with, element strides B, C, F, H, W
+ *   dev_grad_ref, strides_grad_ref, grad_ref_bytes   out, as dev_grad; must not overlap dev_grad
+ *   dev_scratch    cvvdp_*_gradient_wrt_scratch_bytes(h, wrt) bytes (0 for an unknown wrt).  CVVDP_WRT_TEST and CVVDP_WRT_REFERENCE: the
+ *                  sibling's size and layout (image 57.3, one-block video 74.7 bytes per pixel and item, blocks as documented above).
+ *                  CVVDP_WRT_BOTH: behind the per-level regions d[l], ey[l] a second set d_r[l], ey_r[l] of the same sizes, and (blocks)
+ *                  behind the carry a second carry of the same size: (9 + 8 * 4/3) floats = 78.7 bytes per pixel and item for an image,
+ *                  (12 + 10 * 4/3) floats = 101.3 bytes per pixel, frame and item for a clip; blocks add 2 x 12 bytes x filter_len per pixel and
+ *                  batch item.  The steps of a level up to and including the blur's adjoint run once for both sides; the contrast step,
+ *                  the baseband, the pyramid adjoints and the display / FIR adjoint run once per side.
+ * cvvdp_video_gradient_blocks_begin_wrt and every cvvdp_video_gradient_block_wrt of a clip take the same wrt. */
+#define CVVDP_WRT_TEST 1
+#define CVVDP_WRT_REFERENCE 2
+#define CVVDP_WRT_BOTH 3
+size_t cvvdp_image_gradient_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt);
+int cvvdp_image_gradient_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test, const int64_t strides_test[5], const void* dev_ref,
+                             const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
+                             const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
+size_t cvvdp_video_gradient_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt);
+int cvvdp_video_gradient_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test, const int64_t strides_test[5], const void* dev_ref,
+                             const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
+                             const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
+size_t cvvdp_video_gradient_blocks_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt);
+int cvvdp_video_gradient_blocks_begin_wrt(cvvdp_handle* h, int32_t wrt, void* dev_scratch, size_t scratch_bytes, void* stream);
+int cvvdp_video_gradient_block_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test, const int64_t strides_test[5], const void* dev_ref,
+                                   const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
+                                   const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Gradient of the JOD in the model's PARAMETERS, for calibration: dev_acc[b][j] += d JOD[b] / d parameter j over the frames of the block
  * processed last, with the parameters as the parameter file stores them (mask_c and d_max as exponents of 10, xcm_weights as exponents
  * of 2, sensitivity_correction in dB).  Slots j: 0 mask_p, 1 mask_c, 2..5 mask_q[0..3], 6..21 xcm_weights[0..15], 22 d_max,
