@@ -211,6 +211,20 @@ SYMBOLS = {
     "cvvdp_pool_dataset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double),
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvvdp_pool_dataset_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cvvdp_pixel_ssim_gradient_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    # (handle, wrt, test, strides, reference, strides, B, n_frames, total_frames, H, W, args, grad, strides, bytes, grad_ref, strides, bytes,
+    #  scratch, bytes, stream)
+    "cvvdp_pixel_ssim_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SsimArgs),
+                                            C.c_void_p, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
+                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_pixel_msssim_gradient_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    # (.. args, per-frame values, level means, the forward's scratch, bytes, grad ..)
+    "cvvdp_pixel_msssim_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MsssimArgs),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_preview_args_size": (C.c_int32, []),
     "cvvdp_pixel_preview": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(PreviewArgs), C.c_void_p, C.c_size_t, C.c_void_p]),

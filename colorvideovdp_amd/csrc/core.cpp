@@ -86,6 +86,9 @@ struct cvvdp_handle {
   int blocks_wrt = 0;                     // ... and the sides (CVVDP_WRT_*) its begin was called for
   int blocks_key[7] = {};                 // ... and the clip cvvdp_video_gradient_blocks_begin saw: a block call after another clip was configured is refused
   int16_t clip_hist[CVVDP_MAX_FILTER_LEN] = {};
+  // cvvdp_pixel_msssim_gradient: what the last cvvdp_pixel_msssim whose arguments passed ran on
+  bool msssim_ran = false;
+  cvvdp::MsssimForwardKey msssim_key{};
 };
 
 namespace {
@@ -932,9 +935,19 @@ int cvvdp::msssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t
     a.weights[k] = (double)args->weights[k];
   }
   a.msssim = msssim; a.levels = levels;
+  h->msssim_key = MsssimForwardKey{t, r, scratch, B, n_frames, H, W};
+  h->msssim_ran = true;
   return CVVDP_OK;
 }
 int cvvdp::msssim_check_launch(cvvdp_handle* h) { return check_launch(h, "pixel_msssim"); }
+// cvvdp_pixel_ssim_gradient, cvvdp_pixel_msssim_gradient (ssim_grad.hip): the entries check their arguments themselves
+int cvvdp::ssim_grad_fail(cvvdp_handle* h, int code, const char* text) { return fail(h, code, "%s", text); }
+int cvvdp::ssim_grad_check_launch(cvvdp_handle* h, const char* what) { return check_launch(h, what); }
+void cvvdp::ssim_grad_display(const cvvdp_handle* h, DisplayArgs& d) { fill_display(h, d); }
+bool cvvdp::ssim_grad_last_msssim(const cvvdp_handle* h, MsssimForwardKey& key) {
+  key = h->msssim_key;
+  return h->msssim_ran;
+}
 // cvvdp_unpack_rgbe (rgbe.hip) up to the launch
 int cvvdp::rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int32_t H, int32_t W, float* out, int64_t stride_c,
                         int64_t stride_f, RgbeArgs& a) {

@@ -824,4 +824,18 @@ void launch_grad_blur_fwd(const float* in, float* out, int H, int W, int planes,
 int pool_dataset_fail(cvvdp_handle* h, const char* text);
 int pool_dataset_check_launch(cvvdp_handle* h, const char* what);
 
+// ---------------------------------------------------------------- SSIM / MS-SSIM gradient (ssim_grad.hip, ssim_grad_dev.h)
+// The entries check their arguments themselves; core.cpp keeps the error text, hands out the handle's display model, remembers what
+// the last cvvdp_pixel_msssim of a handle ran on (the gradient reads the pooled planes it left) and reads the launch's status.
+struct MsssimForwardKey {
+  const void* test;
+  const void* ref;
+  const void* scratch;
+  int32_t B, n_frames, H, W;
+};
+int ssim_grad_fail(cvvdp_handle* h, int code, const char* text);
+int ssim_grad_check_launch(cvvdp_handle* h, const char* what);
+void ssim_grad_display(const cvvdp_handle* h, DisplayArgs& d);
+bool ssim_grad_last_msssim(const cvvdp_handle* h, MsssimForwardKey& key);
+
 }  // namespace cvvdp

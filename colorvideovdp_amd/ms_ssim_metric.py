@@ -12,10 +12,13 @@ The smaller side of a frame must be larger than 160 (ssim.py:212-215; an asserti
 --full-screen-resize.  Quirk Q8 of ssim_metric holds: size_average=True ends in a plain mean over the batch (ssim.py:240-241), so a
 batched call returns ONE number.  A 1-channel source and different batch sizes of test and reference are refused as in ssim_metric.
 """
+import ctypes
+
 import torch
 
 from . import _capi
 from .psnr_metric import _psnr_base
+from .ssim_grad import ssim_gradient
 from .ssim_metric import refuse_block, refuse_source, ssim_scalars
 from .vq_metric import register_metric, vq_exception
 
@@ -41,9 +44,10 @@ def level_sizes(H, W):
     return out
 
 
-class ms_ssim_metric(_psnr_base):
+class ms_ssim_metric(ssim_gradient, _psnr_base):
     """MS-SSIM on luma: display-encoded values, PU21-encoded (scaled so that 100 cd/m^2 maps to 1) when the display is linear or PQ;
-    the defaults of ms_ssim() with data range 1.  Module docstring: size limit, batch quirk, refusals."""
+    the defaults of ms_ssim() with data range 1.  Module docstring: size limit, batch quirk, refusals.  predict_with_gradient() and
+    differentiable_loss() (ssim_grad.py) make it a loss: the gradient of the score in the test, the reference or both, in HIP."""
 
     metric_colorspace = "display_encoded_100nit"
 
@@ -98,6 +102,32 @@ class ms_ssim_metric(_psnr_base):
         outs = (per_frame.data_ptr(), levels.data_ptr(), acc.data_ptr() if acc is not None else None)
         self._pixel_call("cvvdp_pixel_msssim", h, t, r, code, fmt, B, 3, n, H, W, args, outs, scratch)
         return per_frame
+
+    # ------------------------------------------------------------------ gradient (ssim_grad.py)
+    def _refuse_size(self, method, H, W):
+        if min(H, W) <= MIN_SIDE:
+            raise vq_exception(f"MS-SSIM {method}: frames of {W}x{H}: the smaller side must be larger than {MIN_SIDE} "
+                               "(four 2x downsamplings of an 11-tap window)")
+
+    @staticmethod
+    def _grad_scratch_per_frame(code, B, H, W):
+        lib = _capi.lib()
+        return int(lib.cvvdp_pixel_msssim_scratch_bytes(B, 1, H, W)) + int(lib.cvvdp_pixel_msssim_gradient_scratch_bytes(code, B, 1, H, W))
+
+    def _grad_block(self, lib, h, code, t, st, r, sr, B, n, N, H, W, pargs, acc, outs, stream):
+        """Forward of one block as predict() runs it, keeping its level means and pooled planes; then that block's frames of the
+        gradient, which reads them."""
+        args = self._args(pargs)
+        fbytes = int(lib.cvvdp_pixel_msssim_scratch_bytes(B, n, H, W))
+        fscratch = torch.empty(max(fbytes, 16), dtype=torch.uint8, device=self.device)
+        levels = torch.empty((n, B, LEVELS), dtype=torch.float64, device=self.device)
+        per_frame = self._msssim(h, t, r, _capi.F32, None, B, n, H, W, args, acc, levels=levels, scratch=fscratch)
+        nbytes = int(lib.cvvdp_pixel_msssim_gradient_scratch_bytes(code, B, n, H, W))
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        rc = lib.cvvdp_pixel_msssim_gradient(h, code, t.data_ptr(), st, r.data_ptr(), sr, B, n, N, H, W, ctypes.byref(args),
+                                             per_frame.data_ptr(), levels.data_ptr(), fscratch.data_ptr(), fbytes, *outs,
+                                             scratch.data_ptr(), nbytes, stream)
+        _capi.check(h, rc, "cvvdp_pixel_msssim_gradient")
 
 
 register_metric(ms_ssim_metric)

@@ -14,11 +14,14 @@ here it is refused with a vq_exception.  So are a test and a reference of differ
 ssim.py:131-132; the reference's array source lets a singleton batch through and ssim() then raises) and frames with a height or a
 width of 1 (ssim() squeezes the dimension away and rejects the 3-d tensor, ssim.py:134-139).
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _capi
 from .psnr_metric import _psnr_base
+from .ssim_grad import ssim_gradient
 from .video_source import video_source_array
 from .vq_metric import register_metric, vq_exception
 
@@ -56,7 +59,7 @@ def refuse_block(name, t, r, fmt, C):
         raise vq_exception(f"{name}: test has batch size {t.shape[0]}, reference {r.shape[0]}")
 
 
-class ssim_metric(_psnr_base):
+class ssim_metric(ssim_gradient, _psnr_base):
     """Plain SSIM on luma (ssim_metric.py:17-58): display-encoded values, PU21-encoded (scaled so that 100 cd/m^2 maps to 1) when the
     display is linear or PQ; window 11, sigma 1.5, data range 1, no non-negativity clamp.  Quirks Q8 and Q9: module docstring."""
 
@@ -79,13 +82,7 @@ class ssim_metric(_psnr_base):
 
     def predict_video_source(self, vid_source, frame_padding="replicate"):
         vs, H, W, N, B, is_yuv, raw, h, pargs, _ = self._open(vid_source, self._refuse)
-        s = ssim_scalars()
-        args = _capi.SsimArgs()
-        args.win[:] = s["win"].tolist()
-        args.C1, args.C2 = float(s["C1"]), float(s["C2"])
-        args.luma[:] = s["luma"].tolist()
-        args.pu_p[:] = list(pargs.pu_p)
-        args.pu_L_min, args.pu_L_max, args.pu_norm = pargs.pu_L_min, pargs.pu_L_max, pargs.pu_norm
+        args = self._args(pargs)
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             for t, r, code, fmt, C, n in self._blocks(vs, H, W, N, B, is_yuv, raw, pargs):
@@ -94,9 +91,42 @@ class ssim_metric(_psnr_base):
                 self._ssim(h, t, r, code, fmt, B, n, H, W, args, acc)
         return (acc[0] / N).to(torch.float32), None
 
+    @staticmethod
+    def _args(pargs):
+        """cvvdp_ssim_args from ssim_scalars() and the target and PU21 constants of a cvvdp_psnr_args."""
+        s = ssim_scalars()
+        args = _capi.SsimArgs()
+        args.target = pargs.target
+        args.win[:] = s["win"].tolist()
+        args.C1, args.C2 = float(s["C1"]), float(s["C2"])
+        args.luma[:] = s["luma"].tolist()
+        args.pu_p[:] = list(pargs.pu_p)
+        args.pu_L_min, args.pu_L_max, args.pu_norm = pargs.pu_L_min, pargs.pu_L_max, pargs.pu_norm
+        return args
+
     def _ssim(self, h, t, r, code, fmt, B, n, H, W, args, acc):
         per_frame = torch.empty((n, B), dtype=torch.float64, device=self.device)
         self._pixel_call("cvvdp_pixel_ssim", h, t, r, code, fmt, B, 3, n, H, W, args, (per_frame.data_ptr(), acc.data_ptr()))
+
+    # ------------------------------------------------------------------ gradient (ssim_grad.py)
+    def _refuse_size(self, method, H, W):
+        if H < 2 or W < 2:
+            raise vq_exception(f"SSIM {method}: frames of {W}x{H}: a side of 1 has no SSIM (the reference's ssim() drops the dimension)")
+
+    @staticmethod
+    def _grad_scratch_per_frame(code, B, H, W):
+        lib = _capi.lib()
+        return int(lib.cvvdp_pixel_ssim_scratch_bytes(B, 1, H, W)) + int(lib.cvvdp_pixel_ssim_gradient_scratch_bytes(code, B, 1, H, W))
+
+    def _grad_block(self, lib, h, code, t, st, r, sr, B, n, N, H, W, pargs, acc, outs, stream):
+        """Forward of one block as predict() runs it, then that block's frames of the gradient."""
+        args = self._args(pargs)
+        self._ssim(h, t, r, _capi.F32, None, B, n, H, W, args, acc)
+        nbytes = int(lib.cvvdp_pixel_ssim_gradient_scratch_bytes(code, B, n, H, W))
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        rc = lib.cvvdp_pixel_ssim_gradient(h, code, t.data_ptr(), st, r.data_ptr(), sr, B, n, N, H, W, ctypes.byref(args), *outs,
+                                           scratch.data_ptr(), nbytes, stream)
+        _capi.check(h, rc, "cvvdp_pixel_ssim_gradient")
 
 
 register_metric(ssim_metric)

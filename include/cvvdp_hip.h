@@ -629,6 +629,44 @@ int cvvdp_pool_dataset(cvvdp_handle* h, const float* dev_q, const int64_t* dev_o
 int cvvdp_pool_dataset_loss(cvvdp_handle* h, const double* dev_jod, const double* dev_grad, const double* dev_target, int32_t n,
                             double* dev_loss, double* dev_dloss, void* stream);
 
+/* Gradient of SSIM and MS-SSIM in the frames (csrc/ssim_grad.hip, csrc/ssim_grad_dev.h): d score / d test, d score /
+ * d reference or both, where score is what cvvdp_pixel_ssim / cvvdp_pixel_msssim add to dev_acc for these frames, divided by
+ * total_frames (the clip's length: a block of n_frames <= total_frames frames of it is handed in, frames do not interact).
+ *   wrt                CVVDP_WRT_TEST, CVVDP_WRT_REFERENCE or CVVDP_WRT_BOTH; anything else is CVVDP_E_ARG
+ *   dev_test, dev_ref  float32 [B, 3, n_frames, H, W] with non-negative element strides, as cvvdp_pixel_ssim takes them with CVVDP_F32
+ *   args               the forward's arguments: both targets.  CVVDP_PSNR_AS_IS: slope 1, no clamp, on every display.  CVVDP_PSNR_PU21:
+ *                      d (PU21(forward(V)) / pu_norm) / d V on linear and PQ displays (CVVDP_E_UNSUPPORTED on the others, which the
+ *                      metrics never ask for)
+ *   dev_grad_*         float32, written at strides_grad_* (elements, non-negative, [B, 3, n_frames, H, W]); the last element must lie
+ *                      inside grad_*_bytes.  Only the sides wrt names are read and written
+ *   dev_scratch        cvvdp_pixel_*_gradient_scratch_bytes(wrt, B, n_frames, H, W) bytes (0 for an unknown wrt or a refused size),
+ *                      8-byte aligned.  Layout, items = n_frames * B, Hm x Wm the SSIM map of H x W, NP = 3 (4 for CVVDP_WRT_BOTH):
+ *                        float X[items][H][W], Y[items][H][W]       lumas of test and reference in the target space
+ *                        float coef[NP][items][Hm][Wm]              u dv/dmu1 (dv/dmu2 for CVVDP_WRT_REFERENCE), u dv/de11, u dv/de12, and
+ *                                                                   u dv/dmu2 for CVVDP_WRT_BOTH; reused by every MS-SSIM level
+ *                        MS-SSIM: float dX[level 1..4][sides][items][H_l][W_l]   luma gradients of the pooled levels, sides = 1 (2)
+ * cvvdp_pixel_msssim_gradient reads what cvvdp_pixel_msssim left for the SAME frames: dev_msssim, dev_levels and the pooled planes in
+ * its scratch.  It must follow that call on the same handle with the same dev_test, dev_ref, B, n_frames, H, W and scratch
+ * (CVVDP_E_STATE otherwise) and on the same stream.  A frame with a level mean <= 0 gets an all-zero gradient.
+ * Conventions: torch's subgradient rules (clamp passes at its bounds, relu gives 0 at and below 0); 0 where the reference's autograd
+ * gives NaN or infinity (a PQ sample of exactly 0, a PU21 slope that is not finite, a level mean <= 0).  Gather kernels only: no
+ * atomics, every sum in an order fixed by H and W, the same bits on every run and for every cut of a clip into blocks.  Nothing
+ * synchronises.  Null or misaligned pointers, negative strides, a bad geometry (H or W < 2; MS-SSIM: min(H, W) <= 160), a short
+ * gradient buffer or scratch give CVVDP_E_ARG -- all before any launch.  Added; nothing else changed, so CVVDP_ABI_VERSION stays 14. */
+size_t cvvdp_pixel_ssim_gradient_scratch_bytes(int32_t wrt, int32_t B, int32_t n_frames, int32_t H, int32_t W);
+int cvvdp_pixel_ssim_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_test, const int64_t strides_test[5], const float* dev_ref,
+                              const int64_t strides_ref[5], int32_t B, int32_t n_frames, int32_t total_frames, int32_t H, int32_t W,
+                              const cvvdp_ssim_args* args, float* dev_grad_test, const int64_t strides_grad_test[5], size_t grad_test_bytes,
+                              float* dev_grad_ref, const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch,
+                              size_t scratch_bytes, void* stream);
+size_t cvvdp_pixel_msssim_gradient_scratch_bytes(int32_t wrt, int32_t B, int32_t n_frames, int32_t H, int32_t W);
+int cvvdp_pixel_msssim_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_test, const int64_t strides_test[5], const float* dev_ref,
+                                const int64_t strides_ref[5], int32_t B, int32_t n_frames, int32_t total_frames, int32_t H, int32_t W,
+                                const cvvdp_msssim_args* args, const double* dev_msssim, const double* dev_levels, const void* dev_forward_scratch,
+                                size_t forward_scratch_bytes, float* dev_grad_test, const int64_t strides_grad_test[5], size_t grad_test_bytes,
+                                float* dev_grad_ref, const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch,
+                                size_t scratch_bytes, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
