@@ -634,7 +634,7 @@ __global__ __launch_bounds__(64 * NCH, FEAT ? 2 : 3) void k_band4(BandArgs a) {
 template <bool RAGGED>
 static void launch_band4_w(const BandArgs& a, hipStream_t s) {
   dim3 grid(8 * a.per_xcd);
-  if (a.fsum) {          // features for the ML heads (no heat map, no dump: extract_features refuses the one, core.cpp never sets the other)
+  if (a.fsum) {          // features for the ML heads (no heat map, no dump: extract_features refuses the one, score_host.cpp never sets the other)
     if (a.nch == 4) hipLaunchKernelGGL((k_band4<4, false, RAGGED, false, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_band4<3, false, RAGGED, false, true>), grid, dim3(192), 0, s, a);
   } else if (a.dchr) {   // heat map (with or without the per-pixel dump)

@@ -23,7 +23,7 @@
 //     them -- the top segment starts at row 0 and writes rows 1..6 into their mirror slots too, the bottom segment copies the
 //     mirrored slot (reflect padding of the blurred map = the mirrored row of the horizontally blurred map).
 //
-// Used by launch_band (core.cpp) for even W, no heat map / dump / features; everything else keeps k_band4 + the reduce pass.
+// Used by run_bands (score_host.cpp) for even W, no heat map / dump / features; everything else keeps k_band4 + the reduce pass.
 // The streamed loads are hand-managed like k_band4's (six per row: four neighbour loads of row s+6, two row loads of row s+7;
 // one uniform `s_waitcnt vmcnt(2)` per step); tools/check_band4_isa.py checks this kernel's assembly too.
 #include <type_traits>

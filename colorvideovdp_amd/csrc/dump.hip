@@ -214,7 +214,7 @@ int cvvdp_dump_channels(cvvdp_handle* h, int32_t which, int32_t frame0, int32_t 
       else cvvdp::launch_dump_diff(plan.df[l], s);
     }
   }
-  return cvvdp::dump_check_launch(h);
+  return cvvdp::host_check_launch(h, "dump_channels");
 }
 
 }  // extern "C"

@@ -185,7 +185,7 @@ void blur_pass(const float* in, float* out, int H, int W, int planes, bool verti
   hipLaunchKernelGGL(k_grad_blur, pixel_grid(H, W, planes), dim3(GT), 0, s, b);
 }
 
-// levels finest first, the baseband, then the totals coarsest first: B items of NC channels (NC * B planes fit a grid's y: core.cpp checks)
+// levels finest first, the baseband, then the totals coarsest first: B items of NC channels (NC * B planes fit a grid's y: grad_host.cpp checks)
 template <int NC>
 void launch_chain(const GradChain<NC>& c, hipStream_t s) {
   const int L = c.L, B = c.items;
@@ -246,13 +246,13 @@ void launch_grad_blur_fwd(const float* in, float* out, int H, int W, int planes,
 // ---------------------------------------------------------------- C ABI (include/cvvdp_hip.h)
 extern "C" {
 
-size_t cvvdp_image_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp::grad_scratch(h); }
+size_t cvvdp_image_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp::grad_wrt_scratch(h, 0, CVVDP_WRT_TEST); }
 
 int cvvdp_image_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                          size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
   return cvvdp::run_plan<cvvdp::GradPlan>(
-      [&](auto& p) { return cvvdp::grad_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
-      [&](auto& p) { cvvdp::launch_image_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_check_launch(h); });
+      [&](auto& p) { return cvvdp::grad_prepare(h, cvvdp::test_side(dev_test, strides_test, dev_grad, strides_grad, grad_bytes), dev_scratch, scratch_bytes, p); },
+      [&](auto& p) { cvvdp::launch_image_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::host_check_launch(h, "image_gradient"); });
 }
 
 size_t cvvdp_image_gradient_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt) { return cvvdp::grad_wrt_scratch(h, 0, wrt); }
@@ -261,9 +261,9 @@ int cvvdp_image_gradient_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test,
                              const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
                              const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
   const cvvdp::GradSides sd{wrt, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_ref, strides_ref, dev_grad_ref, strides_grad_ref, grad_ref_bytes};
-  return cvvdp::run_plan<cvvdp::GradPlan>([&](auto& p) { return cvvdp::grad_prepare_wrt(h, sd, dev_scratch, scratch_bytes, p); },
+  return cvvdp::run_plan<cvvdp::GradPlan>([&](auto& p) { return cvvdp::grad_prepare(h, sd, dev_scratch, scratch_bytes, p); },
                                           [&](auto& p) { cvvdp::launch_image_gradient(p, static_cast<hipStream_t>(stream)); },
-                                          [&] { return cvvdp::grad_check_launch(h); });
+                                          [&] { return cvvdp::host_check_launch(h, "image_gradient"); });
 }
 
 }  // extern "C"

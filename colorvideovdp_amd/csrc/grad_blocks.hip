@@ -135,36 +135,36 @@ void launch_grad_blocks_block(const GradBlocksPlan& p, hipStream_t s) {
 // ---------------------------------------------------------------- C ABI (include/cvvdp_hip.h)
 extern "C" {
 
-size_t cvvdp_video_gradient_blocks_scratch_bytes(const cvvdp_handle* h) { return cvvdp::grad_blocks_scratch(h); }
+size_t cvvdp_video_gradient_blocks_scratch_bytes(const cvvdp_handle* h) { return cvvdp::grad_wrt_scratch(h, 2, CVVDP_WRT_TEST); }
 
 int cvvdp_video_gradient_blocks_begin(cvvdp_handle* h, void* dev_scratch, size_t scratch_bytes, void* stream) {
-  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_begin_prepare(h, dev_scratch, scratch_bytes, p); },
+  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_begin_prepare(h, CVVDP_WRT_TEST, dev_scratch, scratch_bytes, p); },
                                                 [&](auto& p) { cvvdp::launch_grad_blocks_begin(p, static_cast<hipStream_t>(stream)); },
-                                                [&] { return cvvdp::grad_blocks_check_launch(h, false); });
+                                                [&] { return cvvdp::grad_blocks_after_launch(h, false); });
 }
 
 int cvvdp_video_gradient_block(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                                size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
   return cvvdp::run_plan<cvvdp::GradBlocksPlan>(
-      [&](auto& p) { return cvvdp::grad_blocks_block_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
-      [&](auto& p) { cvvdp::launch_grad_blocks_block(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_blocks_check_launch(h, true); });
+      [&](auto& p) { return cvvdp::grad_blocks_block_prepare(h, cvvdp::test_side(dev_test, strides_test, dev_grad, strides_grad, grad_bytes), dev_scratch, scratch_bytes, p); },
+      [&](auto& p) { cvvdp::launch_grad_blocks_block(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_blocks_after_launch(h, true); });
 }
 
 size_t cvvdp_video_gradient_blocks_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt) { return cvvdp::grad_wrt_scratch(h, 2, wrt); }
 
 int cvvdp_video_gradient_blocks_begin_wrt(cvvdp_handle* h, int32_t wrt, void* dev_scratch, size_t scratch_bytes, void* stream) {
-  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_begin_prepare_wrt(h, wrt, dev_scratch, scratch_bytes, p); },
+  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_begin_prepare(h, wrt, dev_scratch, scratch_bytes, p); },
                                                 [&](auto& p) { cvvdp::launch_grad_blocks_begin(p, static_cast<hipStream_t>(stream)); },
-                                                [&] { return cvvdp::grad_blocks_check_launch(h, false); });
+                                                [&] { return cvvdp::grad_blocks_after_launch(h, false); });
 }
 
 int cvvdp_video_gradient_block_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test, const int64_t strides_test[5], const void* dev_ref,
                                    const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
                                    const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
   const cvvdp::GradSides sd{wrt, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_ref, strides_ref, dev_grad_ref, strides_grad_ref, grad_ref_bytes};
-  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_block_prepare_wrt(h, sd, dev_scratch, scratch_bytes, p); },
+  return cvvdp::run_plan<cvvdp::GradBlocksPlan>([&](auto& p) { return cvvdp::grad_blocks_block_prepare(h, sd, dev_scratch, scratch_bytes, p); },
                                                 [&](auto& p) { cvvdp::launch_grad_blocks_block(p, static_cast<hipStream_t>(stream)); },
-                                                [&] { return cvvdp::grad_blocks_check_launch(h, true); });
+                                                [&] { return cvvdp::grad_blocks_after_launch(h, true); });
 }
 
 }  // extern "C"

@@ -143,7 +143,7 @@ size_t cvvdp_param_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp:
 int cvvdp_param_gradient(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
   return cvvdp::run_plan<cvvdp::ParamPlan>([&](auto& p) { return cvvdp::param_grad_prepare(h, dq, acc, scratch, scratch_bytes, p); },
                                            [&](auto& p) { cvvdp::launch_param_gradient(p, static_cast<hipStream_t>(stream)); },
-                                           [&] { return cvvdp::param_grad_check_launch(h); });
+                                           [&] { return cvvdp::host_check_launch(h, "param_gradient"); });
 }
 
 }  // extern "C"

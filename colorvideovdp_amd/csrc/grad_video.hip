@@ -140,13 +140,13 @@ void launch_video_gradient(const GradVideoPlan& p, hipStream_t s) {
 // ---------------------------------------------------------------- C ABI (include/cvvdp_hip.h)
 extern "C" {
 
-size_t cvvdp_video_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp::grad_video_scratch(h); }
+size_t cvvdp_video_gradient_scratch_bytes(const cvvdp_handle* h) { return cvvdp::grad_wrt_scratch(h, 1, CVVDP_WRT_TEST); }
 
 int cvvdp_video_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], float* dev_grad, const int64_t strides_grad[5],
                          size_t grad_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
   return cvvdp::run_plan<cvvdp::GradVideoPlan>(
-      [&](auto& p) { return cvvdp::grad_video_prepare(h, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_scratch, scratch_bytes, p); },
-      [&](auto& p) { cvvdp::launch_video_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::grad_video_check_launch(h); });
+      [&](auto& p) { return cvvdp::grad_video_prepare(h, cvvdp::test_side(dev_test, strides_test, dev_grad, strides_grad, grad_bytes), dev_scratch, scratch_bytes, p); },
+      [&](auto& p) { cvvdp::launch_video_gradient(p, static_cast<hipStream_t>(stream)); }, [&] { return cvvdp::host_check_launch(h, "video_gradient"); });
 }
 
 size_t cvvdp_video_gradient_wrt_scratch_bytes(const cvvdp_handle* h, int32_t wrt) { return cvvdp::grad_wrt_scratch(h, 1, wrt); }
@@ -155,9 +155,9 @@ int cvvdp_video_gradient_wrt(cvvdp_handle* h, int32_t wrt, const void* dev_test,
                              const int64_t strides_ref[5], float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes, float* dev_grad_ref,
                              const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch, size_t scratch_bytes, void* stream) {
   const cvvdp::GradSides sd{wrt, dev_test, strides_test, dev_grad, strides_grad, grad_bytes, dev_ref, strides_ref, dev_grad_ref, strides_grad_ref, grad_ref_bytes};
-  return cvvdp::run_plan<cvvdp::GradVideoPlan>([&](auto& p) { return cvvdp::grad_video_prepare_wrt(h, sd, dev_scratch, scratch_bytes, p); },
+  return cvvdp::run_plan<cvvdp::GradVideoPlan>([&](auto& p) { return cvvdp::grad_video_prepare(h, sd, dev_scratch, scratch_bytes, p); },
                                                [&](auto& p) { cvvdp::launch_video_gradient(p, static_cast<hipStream_t>(stream)); },
-                                               [&] { return cvvdp::grad_video_check_launch(h); });
+                                               [&] { return cvvdp::host_check_launch(h, "video_gradient"); });
 }
 
 }  // extern "C"

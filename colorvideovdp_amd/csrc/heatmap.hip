@@ -591,7 +591,7 @@ __global__ __launch_bounds__(256) void k_heat_raw_rows(HeatArgs a, int n_chunk, 
 }
 
 void launch_heat_raw(const HeatArgs& a, hipStream_t s) {
-  if (a.coarse && !a.pixel_layout) {           // (W % 4 == 0: core.cpp heat_l0_fused)
+  if (a.coarse && !a.pixel_layout) {           // (W % 4 == 0: handle.h heat_l0_fused)
     const int n_chunk = (a.W + 1023) / 1024;
     const int chunk_cols = ((a.W / 4 + n_chunk - 1) / n_chunk) * 4;
     const int n_rg = (a.H + kHeatTileRows - 1) / kHeatTileRows;
@@ -628,7 +628,7 @@ void launch_heat_colour(const HeatArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL(k_heat_hist<false>, dim3(gh, a.items), dim3(256), 0, s, a);
   }
   hipLaunchKernelGGL(k_heat_curve, dim3(a.items), dim3(256), 0, s, a);
-  if (a.coarse && !a.pixel_layout) {           // (W % 4 == 0: core.cpp heat_l0_fused)
+  if (a.coarse && !a.pixel_layout) {           // (W % 4 == 0: handle.h heat_l0_fused)
     const int n_chunk = (a.W + 1023) / 1024;
     const int chunk_cols = ((a.W / 4 + n_chunk - 1) / n_chunk) * 4;
     const int n_rg = (a.H + kHeatTileRows - 1) / kHeatTileRows;

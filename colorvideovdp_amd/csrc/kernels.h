@@ -1,4 +1,4 @@
-// Internal launch interface between core.cpp (planning) and the gfx950 kernels.
+// Internal launch interface between the host code (core.cpp and the *_host.cpp files: planning) and the gfx950 kernels.
 // Argument structs are passed by value as kernel arguments (they live in SGPRs / the kernarg
 // segment, so per-band constants cost no LDS and no vector loads).
 #pragma once
@@ -58,6 +58,14 @@ struct DisplayArgs {         // display model, shared by the image and the fused
   int32_t use_lut;
   float lut[256];
 };
+// ---------------------------------------------------------------- what every C entry may ask of the handle (core.cpp)
+// The handle is opaque to the kernel translation units (its definition is csrc/handle.h, host .cpp files only); their C entries reach it
+// through these three.  host_fail: the entry's answer `code`, with the printf-style text cvvdp_last_error returns to the calling thread;
+// host_check_launch: hipGetLastError after the entry's launches, as "<what>: <HIP's text>"; host_display: the handle's display model.
+int host_fail(cvvdp_handle* h, int code, const char* fmt, ...);
+int host_check_launch(cvvdp_handle* h, const char* what);
+void host_display(const cvvdp_handle* h, DisplayArgs& d);
+
 struct PhotoArgs {
   const void* src[2];     // test, ref
   int64_t sb[2], sc[2], sf[2], sh[2], sw[2];  // element strides
@@ -146,11 +154,10 @@ struct ResampleArgs {
 static_assert(sizeof(ResampleArgs) <= 4096, "kernel arguments of the resampling temporal kernel");
 inline bool fir_resampled_has_window(int depth) { return depth == 8 || depth == 12 || depth == 18 || depth == 26; }
 void launch_fir_resampled(const ResampleArgs& a, bool generic, hipStream_t s);
-// core.cpp: argument checks and kernel arguments of cvvdp_fir_resampled_yuv; the error of a launch
+// pixel_host.cpp: argument checks and kernel arguments of cvvdp_fir_resampled_yuv
 int fir_resampled_prepare(cvvdp_handle* h, const void* t, const void* r, const cvvdp_yuv_format* fmt, int32_t H, int32_t W,
                           const int32_t n_src[2], int32_t depth, const float* w_t, const float* w_r, const int32_t* e_t, const int32_t* e_r,
                           int32_t n_out, float* out_t, float* out_r, ResampleArgs& a);
-int fir_resampled_check_launch(cvvdp_handle* h);
 
 // ---------------------------------------------------------------- gaussian pyramid reduce (K2)
 struct ReduceArgs {
@@ -158,7 +165,7 @@ struct ReduceArgs {
   float* out;        // [planes*items][Ho*Wo]
   int32_t H, W, Ho, Wo, n_img;   // n_img = images actually processed per plane
   int32_t img_cap;               // images allocated per plane of the input level (plane stride = img_cap * size)
-  int32_t img_cap_out;           // ... and of the output level (the two differ for level 0 of clips scored in pieces, core.cpp)
+  int32_t img_cap_out;           // ... and of the output level (the two differ for level 0 of clips scored in pieces, score_host.cpp)
   int32_t n_planes;
   float k[5];
 };
@@ -340,11 +347,10 @@ struct PsnrArgs {
 static_assert(sizeof(PsnrArgs) <= 4096, "kernel arguments of the PSNR kernels");
 constexpr int kPsnrTilePx = 256 * 16;      // pixels per workgroup of k_psnr_sse (256 threads x 16 pixels)
 inline int psnr_tiles(int H, int W) { return (int)(((int64_t)H * W + kPsnrTilePx - 1) / kPsnrTilePx); }
-// core.cpp: argument checks and kernel arguments of cvvdp_pixel_sse; the error of a launch
+// pixel_host.cpp: argument checks and kernel arguments of cvvdp_pixel_sse
 int psnr_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
                  const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_psnr_args* args,
                  const double* sse, const void* scratch, size_t scratch_bytes, PsnrArgs& a);
-int psnr_check_launch(cvvdp_handle* h);
 void launch_psnr_sse(const PsnrArgs& a, double* sse, double* mse_acc, hipStream_t s);
 
 // ---------------------------------------------------------------- SSIM metric (ssim.hip)
@@ -367,11 +373,10 @@ inline int ssim_map_size(int n) { return n >= kSsimWin ? n - (kSsimWin - 1) : n;
 inline int ssim_tiles_x(int W) { const int out = W >= kSsimWin ? kSsimCols - (kSsimWin - 1) : kSsimCols; return (ssim_map_size(W) + out - 1) / out; }
 inline int ssim_tiles_y(int H) { return (ssim_map_size(H) + kSsimRows - 1) / kSsimRows; }
 inline int ssim_tiles(int H, int W) { return ssim_tiles_x(W) * ssim_tiles_y(H); }
-// core.cpp: argument checks and kernel arguments of cvvdp_pixel_ssim; the error of a launch
+// pixel_host.cpp: argument checks and kernel arguments of cvvdp_pixel_ssim
 int ssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
                  const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_ssim_args* args,
                  const double* ssim, const void* scratch, size_t scratch_bytes, SsimArgs& a);
-int ssim_check_launch(cvvdp_handle* h);
 void launch_pixel_ssim(const SsimArgs& a, double* ssim, double* acc, hipStream_t s);
 
 // ---------------------------------------------------------------- MS-SSIM metric (msssim.hip)
@@ -421,11 +426,10 @@ inline MsssimLayout msssim_layout(int B, int n_frames, int H, int W) {
   l.total = off;
   return l;
 }
-// core.cpp: argument checks and kernel arguments of cvvdp_pixel_msssim; the error of a launch
+// pixel_host.cpp: argument checks and kernel arguments of cvvdp_pixel_msssim
 int msssim_prepare(cvvdp_handle* h, const void* t, const void* r, int32_t dtype, const int64_t st[5], const int64_t sr[5],
                    const cvvdp_yuv_format* yuv, int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_msssim_args* args,
                    double* msssim, double* levels, void* scratch, size_t scratch_bytes, MsssimArgs& a);
-int msssim_check_launch(cvvdp_handle* h);
 void launch_pixel_msssim(const MsssimArgs& a, double* acc, hipStream_t s);
 
 // ---------------------------------------------------------------- Radiance RGBE frames (rgbe.hip)
@@ -438,10 +442,9 @@ struct RgbeArgs {
   int32_t HW, n_frames;
   int32_t all_vec;          // every frame starts 16-byte aligned on both sides and H * W is a multiple of 4: the grid covers pixel quads
 };
-// core.cpp: argument checks and kernel arguments of cvvdp_unpack_rgbe; the error of a launch
+// pixel_host.cpp: argument checks and kernel arguments of cvvdp_unpack_rgbe
 int rgbe_prepare(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int32_t H, int32_t W, float* out, int64_t stride_c, int64_t stride_f,
                  RgbeArgs& a);
-int rgbe_check_launch(cvvdp_handle* h);
 void launch_unpack_rgbe(const RgbeArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- display-model preview (preview.hip)
@@ -456,10 +459,9 @@ struct PreviewArgs {
   int64_t sr, sf, sc;       // pixels between rows / frames of the canvas; F32: floats between channel planes
 };
 static_assert(sizeof(PreviewArgs) <= 4096, "kernel arguments of the preview kernel");
-// core.cpp: argument checks and kernel arguments of cvvdp_pixel_preview; the error of a launch
+// pixel_host.cpp: argument checks and kernel arguments of cvvdp_pixel_preview
 int preview_prepare(cvvdp_handle* h, const void* src, int32_t dtype, const int64_t st[5], const cvvdp_yuv_format* yuv, int32_t is_ref, int32_t B,
                     int32_t C, int32_t n_frames, int32_t H, int32_t W, const cvvdp_preview_args* args, void* dst, size_t dst_bytes, PreviewArgs& a);
-int preview_check_launch(cvvdp_handle* h);
 void launch_preview(const PreviewArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- --dump-channels mosaics (dump.hip)
@@ -502,7 +504,7 @@ struct DumpDiffArgs {
   DumpQuads q;              // plane = D channel
   DumpCanvas cv;
 };
-struct DumpPlan {           // everything cvvdp_dump_channels launches, filled by core.cpp
+struct DumpPlan {           // everything cvvdp_dump_channels launches, filled by dump_host.cpp
   int32_t which, n_levels;
   int32_t clear;            // 0..255: the byte the canvas is cleared with first; -1: every byte is written by the kernels
   size_t clear_bytes;
@@ -512,10 +514,9 @@ struct DumpPlan {           // everything cvvdp_dump_channels launches, filled b
   DumpLpyrArgs lp[CVVDP_MAX_LEVELS];
   DumpDiffArgs df[CVVDP_MAX_LEVELS];
 };
-// core.cpp: argument checks and kernel arguments of cvvdp_dump_channels / cvvdp_dump_canvas_size; the error of a launch
+// dump_host.cpp: argument checks and kernel arguments of cvvdp_dump_channels / cvvdp_dump_canvas_size; a failed memset as the entry's error
 int dump_canvas(const cvvdp_handle* h, int32_t which, int32_t* height, int32_t* width);
 int dump_prepare(cvvdp_handle* h, int32_t which, int32_t frame0, int32_t n_frames, void* dst, size_t dst_bytes, DumpPlan& plan);
-int dump_check_launch(cvvdp_handle* h);
 int dump_hip_error(cvvdp_handle* h, const char* what, hipError_t e);
 void launch_dump_max(const DumpMaxArgs& a, hipStream_t s);
 void launch_dump_temporal(const DumpTemporalArgs& a, hipStream_t s);
@@ -544,10 +545,9 @@ struct MlHeadArgs {
 };
 // partial sums per batch item: an item of per_item cells starts anywhere in a block, so it touches at most this many blocks
 inline int32_t ml_head_parts(int64_t per_item) { return (int32_t)((per_item - 1) / kMlThreads + 2); }
-// core.cpp: argument checks and kernel arguments of cvvdp_ml_saliency_head; the error of a launch
+// pixel_host.cpp: argument checks and kernel arguments of cvvdp_ml_saliency_head
 int ml_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C, const float* weights, float scale,
                     uint32_t mask, float* q, void* scratch, size_t scratch_bytes, MlHeadArgs& a);
-int ml_head_check_launch(cvvdp_handle* h);
 void launch_ml_head(const MlHeadArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- cvvdp-ml-transformer head (ml_transformer.hip)
@@ -596,7 +596,6 @@ inline size_t mt_head_scratch(int32_t B, int32_t F, int64_t N, int64_t S) {
 }
 int mt_head_prepare(cvvdp_handle* h, const float* feat, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C, const float* weights, float scale,
                     uint32_t mask, float* q, float* y, void* scratch, size_t scratch_bytes, MtHeadArgs& a);
-int mt_head_check_launch(cvvdp_handle* h);
 void launch_mt_head(const MtHeadArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- gradient of the image JOD (grad.hip, grad_dev.h)
@@ -669,7 +668,7 @@ struct GradChain {           // the band chain of every gradient plan: levels fi
   GradRefOut ref[CVVDP_MAX_LEVELS];          // wrt includes the reference: its outputs per level (ey: all but the last) ...
   GradAccumArgs acc_r[CVVDP_MAX_LEVELS];     // ... and its pyramid adjoints
 };
-struct GradPlan {            // everything cvvdp_image_gradient launches, filled by core.cpp
+struct GradPlan {            // everything cvvdp_image_gradient launches, filled by grad_host.cpp
   GradPoolArgs pool;
   GradChain<3> chain;
   GradDisplayArgs dsp;
@@ -693,14 +692,14 @@ int run_plan(Prepare prepare, Launch launch, Check check) {
   return rc;
 }
 static_assert(sizeof(GradBandArgsT<4>) <= 4096 && sizeof(GradDisplayArgs) <= 4096, "kernel arguments of the gradient kernels");
-// core.cpp: scratch size of the configured clip (0: no gradient for it), argument / state checks and the plan; the error of a launch
-size_t grad_scratch(const cvvdp_handle* h);
-int grad_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
-                 size_t scratch_bytes, GradPlan& plan);
-// the same for the *_wrt entries, all routes (route: 0 image, 1 one-block video, 2 blocks); an unknown wrt has no size and is refused
+// the sides of an entry that knows the test side alone (cvvdp_image_gradient, cvvdp_video_gradient, cvvdp_video_gradient_block)
+inline GradSides test_side(const void* test, const int64_t* st, float* grad, const int64_t* sg, size_t grad_bytes) {
+  return GradSides{CVVDP_WRT_TEST, test, st, grad, sg, grad_bytes, nullptr, nullptr, nullptr, nullptr, 0};
+}
+// grad_host.cpp: scratch size of the configured clip for the pixel-gradient routes (route: 0 image, 1 one-block video, 2 blocks; 0 bytes:
+// no gradient for the clip, or an unknown wrt, which the prepare refuses); argument / state checks and the plan
 size_t grad_wrt_scratch(const cvvdp_handle* h, int route, int32_t wrt);
-int grad_prepare_wrt(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradPlan& plan);
-int grad_check_launch(cvvdp_handle* h);
+int grad_prepare(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradPlan& plan);
 void launch_image_gradient(const GradPlan& p, hipStream_t s);
 
 // ---------------------------------------------------------------- gradient of the video JOD (grad_video.hip, grad_video_dev.h)
@@ -731,7 +730,7 @@ struct GradFirAdjArgs {      // G = dJOD/d(level-0 planes) -> dJOD/dV through FI
   float tflip[4 * CVVDP_GRAD_FIR_WL];        // register variant: [c][k], zero from fl on
   DisplayArgs dm;
 };
-struct GradVideoPlan {       // everything cvvdp_video_gradient launches, filled by core.cpp
+struct GradVideoPlan {       // everything cvvdp_video_gradient launches, filled by grad_host.cpp
   GradVideoPoolArgs pool;
   GradChain<4> chain;
   GradFirWeightArgs fw;
@@ -739,11 +738,7 @@ struct GradVideoPlan {       // everything cvvdp_video_gradient launches, filled
   GradFirAdjArgs fir_r;      // the reference side: its G, the reference tensor, its gradient
 };
 static_assert(sizeof(GradFirAdjArgs) <= 4096 && sizeof(GradFirWeightArgs) <= 4096, "kernel arguments of the video gradient kernels");
-size_t grad_video_scratch(const cvvdp_handle* h);
-int grad_video_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
-                       size_t scratch_bytes, GradVideoPlan& plan);
-int grad_video_prepare_wrt(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradVideoPlan& plan);
-int grad_video_check_launch(cvvdp_handle* h);
+int grad_video_prepare(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradVideoPlan& plan);
 // grad.hip: the band chain (levels, baseband, pyramid adjoints) for 4 channels; grad_video.hip: pooling and the FIR / display adjoint
 void launch_grad_chain4(const GradChain<4>& c, hipStream_t s);
 void launch_video_gradient(const GradVideoPlan& p, hipStream_t s);
@@ -764,7 +759,7 @@ struct GradFirStreamArgs {
   int32_t f0, n;            // the block's frames [f0, f0 + n)
   float tfull[4 * CVVDP_MAX_FILTER_LEN];     // slot variant: [c][k] multiplies window position k
 };
-struct GradBlocksPlan {      // everything cvvdp_video_gradient_blocks_begin / _block launch, filled by core.cpp
+struct GradBlocksPlan {      // everything cvvdp_video_gradient_blocks_begin / _block launch, filled by grad_host.cpp
   bool slots;               // the slot variant of the streamed adjoint (symmetric padding, or a filter beyond the register window)
   GradBlocksPoolArgs pool;
   GradChain<4> chain;       // (block only)
@@ -774,13 +769,10 @@ struct GradBlocksPlan {      // everything cvvdp_video_gradient_blocks_begin / _
   GradFirStreamArgs fir_r;  // the reference side, with a carry of its own (carry_floats as well)
 };
 static_assert(sizeof(GradFirStreamArgs) <= 4096, "kernel arguments of the streamed FIR adjoint");
-size_t grad_blocks_scratch(const cvvdp_handle* h);
-int grad_blocks_begin_prepare(cvvdp_handle* h, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
-int grad_blocks_block_prepare(cvvdp_handle* h, const void* test, const int64_t st[5], float* grad, const int64_t sg[5], size_t grad_bytes, void* scratch,
-                              size_t scratch_bytes, GradBlocksPlan& plan);
-int grad_blocks_begin_prepare_wrt(cvvdp_handle* h, int32_t wrt, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
-int grad_blocks_block_prepare_wrt(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
-int grad_blocks_check_launch(cvvdp_handle* h, bool block);      // ... and, after a block's launches, moves the handle on to the next block
+int grad_blocks_begin_prepare(cvvdp_handle* h, int32_t wrt, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
+int grad_blocks_block_prepare(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradBlocksPlan& plan);
+// the error of begin's (block = false) or a block's launches; after a block's, moves the handle on to the next block
+int grad_blocks_after_launch(cvvdp_handle* h, bool block);
 void launch_grad_blocks_begin(const GradBlocksPlan& p, hipStream_t s);
 void launch_grad_blocks_block(const GradBlocksPlan& p, hipStream_t s);
 
@@ -803,7 +795,7 @@ struct ParamRowArgs {        // where the blocks of one level put their rows: sl
   int32_t row_off, nblk, n_frames, B;
 };
 struct ParamReduceArgs { const double* slab; double* acc; int64_t rows_b; };
-struct ParamPlan {           // everything cvvdp_param_gradient launches, filled by core.cpp
+struct ParamPlan {           // everything cvvdp_param_gradient launches, filled by grad_host.cpp
   int32_t NC;               // which of the two chains is filled
   ParamCoefArgs coef;
   GradChain<3> chain3;
@@ -813,29 +805,23 @@ struct ParamPlan {           // everything cvvdp_param_gradient launches, filled
 };
 size_t param_grad_scratch(const cvvdp_handle* h);
 int param_grad_prepare(cvvdp_handle* h, const float* dq, double* acc, void* scratch, size_t scratch_bytes, ParamPlan& plan);
-int param_grad_check_launch(cvvdp_handle* h);
 // grad.hip: k_grad_min and one forward pass of the 13-tap blur, as the pixel gradient's chain launches them
 void launch_grad_min3(const GradBandArgsT<3>& a, hipStream_t s);
 void launch_grad_min4(const GradBandArgsT<4>& a, hipStream_t s);
 void launch_grad_blur_fwd(const float* in, float* out, int H, int W, int planes, bool vertical, const float* w, hipStream_t s);
 
 // ---------------------------------------------------------------- dataset pooling for calibration (pool_dataset.hip, pool_dataset_dev.h)
-// The entries check their arguments themselves; core.cpp keeps the error text (CVVDP_E_ARG) and reads the launch's status.
-int pool_dataset_fail(cvvdp_handle* h, const char* text);
-int pool_dataset_check_launch(cvvdp_handle* h, const char* what);
+// The entries check their arguments themselves and use the handle for the error text alone (host_fail, host_check_launch).
 
 // ---------------------------------------------------------------- SSIM / MS-SSIM gradient (ssim_grad.hip, ssim_grad_dev.h)
-// The entries check their arguments themselves; core.cpp keeps the error text, hands out the handle's display model, remembers what
-// the last cvvdp_pixel_msssim of a handle ran on (the gradient reads the pooled planes it left) and reads the launch's status.
+// The entries check their arguments themselves; pixel_host.cpp remembers what the last cvvdp_pixel_msssim of a handle ran on (the
+// gradient reads the pooled planes it left).
 struct MsssimForwardKey {
   const void* test;
   const void* ref;
   const void* scratch;
   int32_t B, n_frames, H, W;
 };
-int ssim_grad_fail(cvvdp_handle* h, int code, const char* text);
-int ssim_grad_check_launch(cvvdp_handle* h, const char* what);
-void ssim_grad_display(const cvvdp_handle* h, DisplayArgs& d);
 bool ssim_grad_last_msssim(const cvvdp_handle* h, MsssimForwardKey& key);
 
 }  // namespace cvvdp

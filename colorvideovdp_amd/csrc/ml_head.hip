@@ -173,7 +173,7 @@ int cvvdp_ml_saliency_head(cvvdp_handle* h, const float* features, int32_t B, in
   cvvdp::MlHeadArgs a;
   if (int rc = cvvdp::ml_head_prepare(h, features, B, F, Hc, Wc, C, weights, scale, disabled_mask, q, scratch, scratch_bytes, a)) return rc;
   cvvdp::launch_ml_head(a, static_cast<hipStream_t>(stream));
-  return cvvdp::ml_head_check_launch(h);
+  return cvvdp::host_check_launch(h, "ml_saliency_head");
 }
 
 }  // extern "C"

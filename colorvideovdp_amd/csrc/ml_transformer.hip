@@ -412,7 +412,7 @@ int cvvdp_ml_transformer_head(cvvdp_handle* h, const float* features, int32_t B,
   cvvdp::MtHeadArgs a;
   if (int rc = cvvdp::mt_head_prepare(h, features, B, F, Hc, Wc, C, weights, scale, disabled_mask, q, y, scratch, scratch_bytes, a)) return rc;
   cvvdp::launch_mt_head(a, static_cast<hipStream_t>(stream));
-  return cvvdp::mt_head_check_launch(h);
+  return cvvdp::host_check_launch(h, "ml_transformer_head");
 }
 
 }  // extern "C"

@@ -287,7 +287,7 @@ int cvvdp_pixel_msssim(cvvdp_handle* h, const void* t, const void* r, int32_t dt
   cvvdp::MsssimArgs a;
   if (int rc = cvvdp::msssim_prepare(h, t, r, dtype, st, sr, yuv, B, C, n_frames, H, W, args, msssim, levels, scratch, scratch_bytes, a)) return rc;
   cvvdp::launch_pixel_msssim(a, acc, static_cast<hipStream_t>(stream));
-  return cvvdp::msssim_check_launch(h);
+  return cvvdp::host_check_launch(h, "pixel_msssim");
 }
 
 }  // extern "C"

@@ -109,34 +109,34 @@ int cvvdp_pool_dataset(cvvdp_handle* h, const float* dev_q, const int64_t* dev_o
   using namespace cvvdp;
   if (!h) return CVVDP_E_ARG;
   if (!dev_q || !dev_offset || !dev_shape || !dev_theta || !beta || !dev_jod || !dev_grad)
-    return pool_dataset_fail(h, "pool_dataset: null argument (only dev_index may be null)");
+    return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset: null argument (only dev_index may be null)");
   if (misaligned(dev_offset, 8) || misaligned(dev_theta, 8) || misaligned(dev_jod, 8) || misaligned(dev_grad, 8))
-    return pool_dataset_fail(h, "pool_dataset: dev_offset, dev_theta, dev_jod and dev_grad must be 8-byte aligned");
+    return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset: dev_offset, dev_theta, dev_jod and dev_grad must be 8-byte aligned");
   if (misaligned(dev_q, 4) || misaligned(dev_shape, 4) || misaligned(dev_index, 4))
-    return pool_dataset_fail(h, "pool_dataset: dev_q, dev_shape and dev_index must be 4-byte aligned");
-  if (n < 1) return pool_dataset_fail(h, "pool_dataset: n must be at least 1");
+    return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset: dev_q, dev_shape and dev_index must be 4-byte aligned");
+  if (n < 1) return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset: n must be at least 1");
   if (!(beta[0] > 0.0) || !(beta[1] > 0.0) || !(beta[2] > 0.0))
-    return pool_dataset_fail(h, "pool_dataset: beta_sch, beta_tch and beta_t must be positive");
+    return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset: beta_sch, beta_tch and beta_t must be positive");
   PoolDatasetArgs a;
   a.q = dev_q; a.offset = dev_offset; a.shape = dev_shape; a.index = dev_index; a.theta = dev_theta;
   a.beta.sch = beta[0]; a.beta.tch = beta[1]; a.beta.t = beta[2];
   a.jod = dev_jod; a.grad = dev_grad;
   hipLaunchKernelGGL(k_pool_dataset, dim3(n), dim3(kPdThreads), 0, static_cast<hipStream_t>(stream), a);
-  return pool_dataset_check_launch(h, "pool_dataset");
+  return host_check_launch(h, "pool_dataset");
 }
 
 int cvvdp_pool_dataset_loss(cvvdp_handle* h, const double* dev_jod, const double* dev_grad, const double* dev_target, int32_t n,
                             double* dev_loss, double* dev_dloss, void* stream) {
   using namespace cvvdp;
   if (!h) return CVVDP_E_ARG;
-  if (!dev_jod || !dev_grad || !dev_target || !dev_loss || !dev_dloss) return pool_dataset_fail(h, "pool_dataset_loss: null argument");
+  if (!dev_jod || !dev_grad || !dev_target || !dev_loss || !dev_dloss) return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset_loss: null argument");
   if (misaligned(dev_jod, 8) || misaligned(dev_grad, 8) || misaligned(dev_target, 8) || misaligned(dev_loss, 8) || misaligned(dev_dloss, 8))
-    return pool_dataset_fail(h, "pool_dataset_loss: every pointer must be 8-byte aligned");
-  if (n < 1) return pool_dataset_fail(h, "pool_dataset_loss: n must be at least 1");
+    return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset_loss: every pointer must be 8-byte aligned");
+  if (n < 1) return host_fail(h, CVVDP_E_ARG, "%s", "pool_dataset_loss: n must be at least 1");
   PoolLossArgs a;
   a.jod = dev_jod; a.grad = dev_grad; a.target = dev_target; a.n = n; a.loss = dev_loss; a.dloss = dev_dloss;
   hipLaunchKernelGGL(k_pool_dataset_loss, dim3(1), dim3(kPdThreads), 0, static_cast<hipStream_t>(stream), a);
-  return pool_dataset_check_launch(h, "pool_dataset_loss");
+  return host_check_launch(h, "pool_dataset_loss");
 }
 
 }  // extern "C"

@@ -219,7 +219,7 @@ int cvvdp_pixel_preview(cvvdp_handle* h, const void* src, int32_t dtype, const i
   cvvdp::PreviewArgs a;
   if (int rc = cvvdp::preview_prepare(h, src, dtype, st, yuv, is_ref, B, C, n_frames, H, W, args, dst, dst_bytes, a)) return rc;
   cvvdp::launch_preview(a, static_cast<hipStream_t>(stream));
-  return cvvdp::preview_check_launch(h);
+  return cvvdp::host_check_launch(h, "pixel_preview");
 }
 
 }  // extern "C"

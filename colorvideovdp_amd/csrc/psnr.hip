@@ -142,7 +142,7 @@ int cvvdp_pixel_sse(cvvdp_handle* h, const void* t, const void* r, int32_t dtype
   cvvdp::PsnrArgs a;
   if (int rc = cvvdp::psnr_prepare(h, t, r, dtype, st, sr, yuv, B, C, n_frames, H, W, args, sse, scratch, scratch_bytes, a)) return rc;
   cvvdp::launch_psnr_sse(a, sse, mse_acc, static_cast<hipStream_t>(stream));
-  return cvvdp::psnr_check_launch(h);
+  return cvvdp::host_check_launch(h, "pixel_sse");
 }
 
 }  // extern "C"

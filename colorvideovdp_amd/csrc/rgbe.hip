@@ -76,7 +76,7 @@ int cvvdp_unpack_rgbe(cvvdp_handle* h, const void* rgbe, int32_t n_frames, int32
   cvvdp::RgbeArgs a;
   if (int rc = cvvdp::rgbe_prepare(h, rgbe, n_frames, H, W, out, stride_c, stride_f, a)) return rc;
   cvvdp::launch_unpack_rgbe(a, static_cast<hipStream_t>(stream));
-  return cvvdp::rgbe_check_launch(h);
+  return cvvdp::host_check_launch(h, "unpack_rgbe");
 }
 
 }  // extern "C"

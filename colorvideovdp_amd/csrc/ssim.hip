@@ -185,7 +185,7 @@ int cvvdp_pixel_ssim(cvvdp_handle* h, const void* t, const void* r, int32_t dtyp
   cvvdp::SsimArgs a;
   if (int rc = cvvdp::ssim_prepare(h, t, r, dtype, st, sr, yuv, B, C, n_frames, H, W, args, ssim, scratch, scratch_bytes, a)) return rc;
   cvvdp::launch_pixel_ssim(a, ssim, acc, static_cast<hipStream_t>(stream));
-  return cvvdp::ssim_check_launch(h);
+  return cvvdp::host_check_launch(h, "pixel_ssim");
 }
 
 }  // extern "C"

@@ -316,7 +316,7 @@ int sg_prepare(const char* what, const SgCall& c, const cvvdp_ssim_args* sa, boo
   char msg[256];
   auto fail = [&](int code, const char* text) {
     snprintf(msg, sizeof msg, "%s: %s", what, text);
-    return ssim_grad_fail(c.h, code, msg);
+    return host_fail(c.h, code, "%s", msg);
   };
   if (!c.h) return CVVDP_E_STATE;
   if (!wrt_known(c.wrt)) return fail(CVVDP_E_ARG, "wrt is none of CVVDP_WRT_TEST, CVVDP_WRT_REFERENCE, CVVDP_WRT_BOTH");
@@ -349,10 +349,10 @@ int sg_prepare(const char* what, const SgCall& c, const cvvdp_ssim_args* sa, boo
   lay = sg_layout(c.wrt, c.B, c.n_frames, c.H, c.W, multi_scale);
   if (c.scratch_bytes < lay.total) return fail(CVVDP_E_ARG, "scratch too small");
   DisplayArgs dm{};
-  ssim_grad_display(c.h, dm);
+  host_display(c.h, dm);
   if (sa->target == CVVDP_PSNR_PU21 && dm.eotf != CVVDP_EOTF_LINEAR && dm.eotf != CVVDP_EOTF_PQ)
     return fail(CVVDP_E_UNSUPPORTED, "the PU21 target has a gradient on linear and PQ displays only");
-  // sources, strides, display model and PU21 constants as the forward takes them (core.cpp ssim_prepare; its own scratch is not used)
+  // sources, strides, display model and PU21 constants as the forward takes them (pixel_host.cpp ssim_prepare; its own scratch is not used)
   char* base = static_cast<char*>(c.scratch);
   if (int rc = ssim_prepare(c.h, c.src[0], c.src[1], CVVDP_F32, c.ss[0], c.ss[1], nullptr, c.B, 3, c.n_frames, c.H, c.W, sa,
                             reinterpret_cast<const double*>(base), base, c.scratch_bytes, la.s))
@@ -439,7 +439,7 @@ int cvvdp_pixel_ssim_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_tes
   SgLevelArgs a = level_args(c, args, H, W, reinterpret_cast<float*>(static_cast<char*>(dev_scratch) + lay.coef));
   a.X = la.X; a.Y = la.Y;
   launch_level(c, a, oa, true, s);
-  return ssim_grad_check_launch(h, "pixel_ssim_gradient");
+  return host_check_launch(h, "pixel_ssim_gradient");
 }
 
 int cvvdp_pixel_msssim_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_test, const int64_t strides_test[5], const float* dev_ref,
@@ -456,18 +456,18 @@ int cvvdp_pixel_msssim_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_t
   SgLayout lay{};
   if (int rc = sg_prepare("pixel_msssim_gradient", c, args ? &args->ssim : nullptr, true, la, oa, lay)) return rc;
   if (!dev_msssim || !dev_levels || !dev_forward_scratch)
-    return ssim_grad_fail(h, CVVDP_E_ARG, "pixel_msssim_gradient: null argument");
+    return host_fail(h, CVVDP_E_ARG, "%s", "pixel_msssim_gradient: null argument");
   if (misaligned(dev_msssim, 8) || misaligned(dev_levels, 8) || misaligned(dev_forward_scratch, 8))
-    return ssim_grad_fail(h, CVVDP_E_ARG, "pixel_msssim_gradient: dev_msssim, dev_levels and the forward's scratch must be 8-byte aligned");
+    return host_fail(h, CVVDP_E_ARG, "%s", "pixel_msssim_gradient: dev_msssim, dev_levels and the forward's scratch must be 8-byte aligned");
   const MsssimLayout fl = msssim_layout(B, n_frames, H, W);
-  if (forward_scratch_bytes < fl.total) return ssim_grad_fail(h, CVVDP_E_ARG, "pixel_msssim_gradient: the forward's scratch is too small");
+  if (forward_scratch_bytes < fl.total) return host_fail(h, CVVDP_E_ARG, "%s", "pixel_msssim_gradient: the forward's scratch is too small");
   // the pooled planes must be those of the same block: the last cvvdp_pixel_msssim of this handle ran on this scratch and geometry
   MsssimForwardKey key{};
   if (!ssim_grad_last_msssim(h, key))
-    return ssim_grad_fail(h, CVVDP_E_STATE, "pixel_msssim_gradient: cvvdp_pixel_msssim has not run on this handle");
+    return host_fail(h, CVVDP_E_STATE, "%s", "pixel_msssim_gradient: cvvdp_pixel_msssim has not run on this handle");
   if (key.scratch != dev_forward_scratch || key.B != B || key.n_frames != n_frames || key.H != H || key.W != W || key.test != dev_test ||
       key.ref != dev_ref)
-    return ssim_grad_fail(h, CVVDP_E_STATE, "pixel_msssim_gradient: the last cvvdp_pixel_msssim ran on other frames, another geometry or another scratch");
+    return host_fail(h, CVVDP_E_STATE, "%s", "pixel_msssim_gradient: the last cvvdp_pixel_msssim ran on other frames, another geometry or another scratch");
   hipStream_t s = static_cast<hipStream_t>(stream);
   launch_luma(la, s);
   char* base = static_cast<char*>(dev_scratch);
@@ -488,7 +488,7 @@ int cvvdp_pixel_msssim_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_t
     if (k < kMsLevels - 1) { a.Hn = fl.H[k + 1]; a.Wn = fl.W[k + 1]; }
     launch_level(c, a, oa, k == 0, s);
   }
-  return ssim_grad_check_launch(h, "pixel_msssim_gradient");
+  return host_check_launch(h, "pixel_msssim_gradient");
 }
 
 }  // extern "C"

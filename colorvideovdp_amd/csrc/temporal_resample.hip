@@ -132,7 +132,7 @@ int cvvdp_fir_resampled_yuv(cvvdp_handle* h, const void* t, const void* r, const
   cvvdp::ResampleArgs a;
   if (int rc = cvvdp::fir_resampled_prepare(h, t, r, fmt, H, W, n_src, depth, w_t, w_r, e_t, e_r, n_out, out_t, out_r, a)) return rc;
   cvvdp::launch_fir_resampled(a, generic != 0 || !cvvdp::fir_resampled_has_window(depth), static_cast<hipStream_t>(stream));
-  return cvvdp::fir_resampled_check_launch(h);
+  return cvvdp::host_check_launch(h, "fir resampled");
 }
 
 }  // extern "C"

@@ -75,7 +75,7 @@ def rho_bands(W, H, ppd):
 
 
 def segment_height(W_l, H_l, frames, batch, is_video):
-    """Rows of a row segment of a level, csrc/core.cpp cvvdp_configure "Row segments" (lines 494-516), for a plain clip (no heat map) of
+    """Rows of a row segment of a level, csrc/core.cpp cvvdp_configure "Row segments", for a plain clip (no heat map) of
     `frames` frames in all, on the routes the probes force (fuse_mode 1 and 2 both keep this rule: the fused levels' own rule is skipped
     under fuse_mode 1).  Levels without the 13-tap blur's vec4 kernels (under 16 rows or columns) use the same rule on 244-column strips."""
     vec4 = H_l > BLUR_PAD and W_l > BLUR_PAD and W_l >= 16 and H_l >= 16

@@ -643,7 +643,7 @@ def case_rho(name):
 
 
 def heat_l0_fused(W, levels):
-    """csrc/core.cpp heat_l0_fused: the finishing kernels add the expanded level-1 reconstruction themselves."""
+    """csrc/handle.h heat_l0_fused: the finishing kernels add the expanded level-1 reconstruction themselves."""
     return levels >= 2 and W % 4 == 0 and (W + 1) // 2 >= 2
 
 

@@ -1,19 +1,22 @@
 // Host-side sanitizer / out-of-bounds harness of the C ABI (VERDICT r2 "next" #9).  Test infrastructure, CPU only.
 //
-// csrc/core.cpp (planning of the workspace, of the pyramid geometry, of segments and strips; construction of every kernel's
-// argument struct: tap tables, history tables, CSF rows, plane offsets) is compiled UNCHANGED with
-// -fsanitize=address,undefined and linked with this file instead of the HIP runtime and the kernels:
+// The host files of csrc/ (core.cpp and the *_host.cpp files: planning of the workspace, of the pyramid geometry, of segments and
+// strips; construction of every kernel's argument struct: tap tables, history tables, CSF rows, plane offsets) are compiled UNCHANGED
+// with -fsanitize=address,undefined and linked with this file instead of the HIP runtime and the kernels:
 //   * the hip* calls succeed and do nothing (streams / events are counted so that leaks show up),
 //   * every launch_* stub checks that each buffer the kernel would touch lies inside the bound workspace (extents derived from
 //     the struct's own geometry), that strips x segments cover the level, and that the tables are within their arrays.
 //   * the five gradient prepares (image, one-block video, begin / block of the block-by-block route, parameters) are called after
 //     a clip they accept was scored, with a fake scratch of exactly the size the route asks for: every pointer of every kernel
 //     argument lies in the scratch, the workspace or the caller's buffers, the scratch's regions lie apart, one byte less is refused.
+//     The four pixel routes are called with wrt drawn per clip from test, reference and both: the reference side's planes, carry and
+//     buffers are held to the extents of their test-side twins, and with both sides the two sets lie apart.
 // The driver sweeps a few thousand random clip configurations (sizes 2..4500 and beyond, every frame rate, block sizes, heat-map
 // modes, features mode, batches, shards) through the whole call sequence of the Python mirror.  Exit code 0 = no finding.
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
-//       colorvideovdp_amd/csrc/core.cpp tests/native/host_sanitize.cpp -o host_sanitize && ./host_sanitize [n_cases] [seed]
+//       colorvideovdp_amd/csrc/{core,score_host,pixel_host,grad_host,dump_host}.cpp tests/native/host_sanitize.cpp -o host_sanitize \
+//       && ./host_sanitize [n_cases] [seed]
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -218,12 +221,15 @@ void launch_heat_colour(const HeatArgs& a, hipStream_t) { chk_heat(a); }
 }  // namespace cvvdp
 
 // ---------------------------------------------------------------- gradient plans
-// The five prepares of core.cpp fill whole plans; nothing is launched.  Every pointer of every kernel argument must lie, with the extent
-// the kernel indexes, inside the caller's scratch, the workspace, or the buffer it was handed; and the regions of one plan inside the
-// scratch (a region = what starts at one address) must not run into each other.
+// The five prepares of grad_host.cpp fill whole plans; nothing is launched.  Every pointer of every kernel argument must lie, with the
+// extent the kernel indexes, inside the caller's scratch, the workspace, or the buffer it was handed; and the regions of one plan inside
+// the scratch (a region = what starts at one address) must not run into each other.  The reference side's regions carry names of their
+// own when the plan has both sides (d_r, ey_r, carry_r: they must lie apart from d, ey, carry), and the test side's names when the
+// reference stands alone (the layout then puts them where the test's would be).
 struct Buf { const char* name; uintptr_t lo; size_t bytes; };
 static Buf g_scratch{"scratch", uintptr_t(5) << 44, 0}, g_test{"test", uintptr_t(7) << 44, 0}, g_grad{"gradient", uintptr_t(9) << 44, 0},
-    g_dq{"dq", uintptr_t(11) << 44, 0}, g_acc{"acc", uintptr_t(13) << 44, 0};
+    g_dq{"dq", uintptr_t(11) << 44, 0}, g_acc{"acc", uintptr_t(13) << 44, 0}, g_ref{"reference", uintptr_t(15) << 44, 0},
+    g_grad_r{"reference gradient", uintptr_t(17) << 44, 0};
 struct Span { uintptr_t lo, hi; const char* what; };
 static std::vector<Span> g_spans;
 static void in_buf(const Buf& b, const void* p, size_t bytes, const char* what) {
@@ -281,6 +287,27 @@ static void chk_chain(const GradChain<NC>& c, bool outputs) {
     if (a.d_f) { REQUIRE(a.H == (a.Hf + 1) / 2 && a.W == (a.Wf + 1) / 2, "chain total %d: finer level", l); in_scratch(a.d_f, (size_t)NC * B * a.Hf * a.Wf, "d"); in_scratch(a.ey_f, (size_t)B * a.Hf * a.Wf, "ey"); }
     if (a.tot_c) { REQUIRE(a.Hc == (a.H + 1) / 2 && a.Wc == (a.W + 1) / 2, "chain total %d: coarser level", l); in_scratch(a.tot_c, (size_t)NC * B * a.Hc * a.Wc, "d"); }
   }
+  if (!(c.wrt & CVVDP_WRT_REFERENCE)) return;
+  // the reference side: its own d / ey per level and its own pyramid adjoints, with the extents of the test side's
+  const bool both = c.wrt == CVVDP_WRT_BOTH;
+  const char* const dn = both ? "d_r" : "d";
+  const char* const eyn = both ? "ey_r" : "ey";
+  for (int l = 0; l < L; ++l) {
+    const GradAccumArgs& t = c.acc[l];
+    const GradAccumArgs& a = c.acc_r[l];
+    const size_t P = (size_t)t.H * t.W;
+    in_scratch(c.ref[l].d, NC * B * P, dn);
+    if (l + 1 < L) in_scratch(c.ref[l].ey, B * P, eyn);
+    REQUIRE(both == (c.ref[l].d != (l + 1 < L ? c.band[l].d : b.d)) && (l + 1 == L || both == (c.ref[l].ey != c.band[l].ey)), "chain level %d: the reference's planes %s the test's", l,
+            both ? "are" : "are not");
+    REQUIRE(a.B == B && a.H == t.H && a.W == t.W && a.Hf == t.Hf && a.Wf == t.Wf && a.Hc == t.Hc && a.Wc == t.Wc, "chain reference total %d: geometry", l);
+    REQUIRE((l == 0) == !a.d_f && (l == 0) == !a.ey_f && (l + 1 == L) == !a.tot_c, "chain reference total %d: which neighbours", l);
+    REQUIRE(a.d == c.ref[l].d && (l == 0 || (a.d_f == c.ref[l - 1].d && a.ey_f == c.ref[l - 1].ey)) && (l + 1 == L || a.tot_c == c.ref[l + 1].d),
+            "chain reference total %d: reads or writes other planes than the reference's", l);
+    in_scratch(a.d, NC * B * P, dn);
+    if (a.d_f) { in_scratch(a.d_f, (size_t)NC * B * a.Hf * a.Wf, dn); in_scratch(a.ey_f, (size_t)B * a.Hf * a.Wf, eyn); }
+    if (a.tot_c) in_scratch(a.tot_c, (size_t)NC * B * a.Hc * a.Wc, dn);
+  }
 }
 static void chk_plan(const GradPlan& p) {
   ++g_launches;
@@ -288,21 +315,28 @@ static void chk_plan(const GradPlan& p) {
   in_ws(po.q, (size_t)po.B * 3 * po.L, "image pool Q_per_ch"); in_scratch(po.coef, (size_t)po.B * 3 * po.L, "coef");
   REQUIRE(po.B == p.chain.items && po.L == p.chain.L, "image plan: pool and chain disagree");
   chk_chain(p.chain, true);
-  const GradDisplayArgs& d = p.dsp;
-  chk_display(d.dm);
-  in_scratch(d.tot, (size_t)3 * d.B * d.H * d.W, "d");
-  in_buf(g_test, d.test, strided_bytes(d.B, 1, d.H, d.W, d.tb, d.tc, 0, d.th, d.tw), "image test"); in_buf(g_grad, d.grad, strided_bytes(d.B, 1, d.H, d.W, d.gb, d.gc, 0, d.gh, d.gw), "image gradient");
+  const int wrt = p.chain.wrt;
+  auto side = [&](const GradDisplayArgs& d, const float* tot, const char* tot_name, const Buf& tensor, const Buf& grad) {
+    chk_display(d.dm);
+    REQUIRE(d.B == po.B && d.tot == tot, "image plan: a side's batch or total");
+    in_scratch(d.tot, (size_t)3 * d.B * d.H * d.W, tot_name);
+    in_buf(tensor, d.test, strided_bytes(d.B, 1, d.H, d.W, d.tb, d.tc, 0, d.th, d.tw), "image tensor"); in_buf(grad, d.grad, strided_bytes(d.B, 1, d.H, d.W, d.gb, d.gc, 0, d.gh, d.gw), "image gradient");
+  };
+  if (wrt & CVVDP_WRT_TEST) side(p.dsp, p.chain.acc[0].d, "d", g_test, g_grad);
+  if (wrt & CVVDP_WRT_REFERENCE) side(p.dsp_r, p.chain.acc_r[0].d, wrt == CVVDP_WRT_BOTH ? "d_r" : "d", g_ref, g_grad_r);
   spans_disjoint();
 }
 static void chk_vpool(const GradVideoPoolArgs& po, int coef_items) {
   in_ws(po.q, (size_t)po.B * 4 * po.F * po.L, "video pool Q_per_ch");
   if (coef_items) in_scratch(po.coef, (size_t)coef_items * 4 * po.L, "coef");
 }
-static void chk_fir_adj(const GradFirAdjArgs& a, int items) {
+// one side of a clip's plan: G is that side's total of level 0 (g_name: its region), tensor and gradient that side's buffers
+static void chk_fir_adj(const GradFirAdjArgs& a, int items, const float* G, const char* g_name, const Buf& tensor, const Buf& grad) {
   chk_display(a.dm);
   REQUIRE(a.fl >= 1 && a.fl <= CVVDP_MAX_FILTER_LEN && (a.reg_wl == 0 || (a.reg_wl >= a.fl && a.reg_wl <= CVVDP_GRAD_FIR_WL)), "fir adjoint: fl %d, window %d", a.fl, a.reg_wl);
-  in_scratch(a.G, (size_t)4 * items * a.H * a.W, "d");
-  in_buf(g_test, a.test, strided_bytes(a.B, a.F, a.H, a.W, a.tb, a.tc, a.tf, a.th, a.tw), "clip test"); in_buf(g_grad, a.grad, strided_bytes(a.B, a.F, a.H, a.W, a.gb, a.gc, a.gf, a.gh, a.gw), "clip gradient");
+  REQUIRE(a.G == G, "fir adjoint: reads another total than its side's");
+  in_scratch(a.G, (size_t)4 * items * a.H * a.W, g_name);
+  in_buf(tensor, a.test, strided_bytes(a.B, a.F, a.H, a.W, a.tb, a.tc, a.tf, a.th, a.tw), "clip tensor"); in_buf(grad, a.grad, strided_bytes(a.B, a.F, a.H, a.W, a.gb, a.gc, a.gf, a.gh, a.gw), "clip gradient");
 }
 static void chk_fir_weights(const GradFirWeightArgs& w, size_t n_floats) {
   in_scratch(w.wt, n_floats, "wt");
@@ -310,35 +344,48 @@ static void chk_fir_weights(const GradFirWeightArgs& w, size_t n_floats) {
 }
 static void chk_plan(const GradVideoPlan& p) {
   ++g_launches;
-  const GradFirAdjArgs& f = p.fir;
-  REQUIRE(p.chain.items == f.F * f.B && p.pool.F == f.F && p.pool.B == f.B, "video plan: items");
-  chk_vpool(p.pool, p.chain.items);
+  const int wrt = p.chain.wrt;
   chk_chain(p.chain, true);
-  if (f.reg_wl == 0) { chk_fir_weights(p.fw, (size_t)4 * f.F * f.F); REQUIRE(f.wt == p.fw.wt && p.fw.F == f.F && p.fw.fl == f.fl, "video plan: weight table"); }
-  chk_fir_adj(f, p.chain.items);
+  auto side = [&](const GradFirAdjArgs& f, const float* G, const char* g_name, const Buf& tensor, const Buf& grad) {
+    REQUIRE(p.chain.items == f.F * f.B && p.pool.F == f.F && p.pool.B == f.B, "video plan: items");
+    if (f.reg_wl == 0) { chk_fir_weights(p.fw, (size_t)4 * f.F * f.F); REQUIRE(f.wt == p.fw.wt && p.fw.F == f.F && p.fw.fl == f.fl, "video plan: weight table"); }
+    chk_fir_adj(f, p.chain.items, G, g_name, tensor, grad);
+  };
+  chk_vpool(p.pool, p.chain.items);
+  if (wrt & CVVDP_WRT_TEST) side(p.fir, p.chain.acc[0].d, "d", g_test, g_grad);
+  if (wrt & CVVDP_WRT_REFERENCE) side(p.fir_r, p.chain.acc_r[0].d, wrt == CVVDP_WRT_BOTH ? "d_r" : "d", g_ref, g_grad_r);
   spans_disjoint();
 }
-static void chk_plan_begin(const GradBlocksPlan& p) {
+static void chk_plan_begin(const GradBlocksPlan& p, int wrt) {
   ++g_launches;
   chk_vpool(p.pool.p, 0);
   in_scratch(p.pool.sum, (size_t)2 * p.pool.p.B, "sum");
   if (p.slots && p.fw.fl > 1) chk_fir_weights(p.fw, (size_t)4 * (p.fw.fl - 1) * p.fw.fl);
-  in_scratch(p.fir.carry, p.carry_floats, "carry");
+  in_scratch(p.fir.carry, p.carry_floats, "carry");      // (one side: one carry, whichever side it serves)
+  if (wrt == CVVDP_WRT_BOTH) in_scratch(p.fir_r.carry, p.carry_floats, "carry_r");
+  else REQUIRE(!p.fir_r.carry, "begin plan: a second carry for one side");
   spans_disjoint();
 }
 static void chk_plan_block(const GradBlocksPlan& p) {
   ++g_launches;
-  const GradFirStreamArgs& s = p.fir;
-  const GradFirAdjArgs& f = s.a;
-  REQUIRE(p.chain.items == s.n * f.B && p.pool.n == s.n && p.pool.q0 == s.f0 && s.f0 >= 0 && s.f0 + s.n <= f.F, "block plan: frames [%d, %d) of %d", s.f0, s.f0 + s.n, f.F);
-  REQUIRE(p.slots == (f.reg_wl == 0), "block plan: variant");
+  const int wrt = p.chain.wrt;
+  const GradFirAdjArgs& f0 = (wrt & CVVDP_WRT_TEST) ? p.fir.a : p.fir_r.a;      // (geometry: the same on both sides)
   chk_vpool(p.pool.p, p.chain.items);
-  in_scratch(p.pool.sum, (size_t)2 * f.B, "sum");
+  in_scratch(p.pool.sum, (size_t)2 * f0.B, "sum");
   chk_chain(p.chain, true);
-  chk_fir_adj(f, p.chain.items);
-  in_scratch(s.carry, (size_t)f.fl * 3 * f.B * f.H * f.W, "carry");
-  REQUIRE(p.carry_floats == (size_t)f.fl * 3 * f.B * f.H * f.W, "block plan: carry of %zu floats", p.carry_floats);
-  if (p.slots && f.fl > 1) in_scratch(s.padw, (size_t)4 * (f.fl - 1) * f.fl, "wt");
+  auto side = [&](const GradFirStreamArgs& s, const float* G, const char* g_name, const char* carry_name, const Buf& tensor, const Buf& grad) {
+    const GradFirAdjArgs& f = s.a;
+    REQUIRE(p.chain.items == s.n * f.B && p.pool.n == s.n && p.pool.q0 == s.f0 && s.f0 >= 0 && s.f0 + s.n <= f.F, "block plan: frames [%d, %d) of %d", s.f0, s.f0 + s.n, f.F);
+    REQUIRE(p.slots == (f.reg_wl == 0), "block plan: variant");
+    chk_fir_adj(f, p.chain.items, G, g_name, tensor, grad);
+    in_scratch(s.carry, (size_t)f.fl * 3 * f.B * f.H * f.W, carry_name);
+    REQUIRE(p.carry_floats == (size_t)f.fl * 3 * f.B * f.H * f.W, "block plan: carry of %zu floats", p.carry_floats);
+    if (p.slots && f.fl > 1) in_scratch(s.padw, (size_t)4 * (f.fl - 1) * f.fl, "wt");
+  };
+  const bool both = wrt == CVVDP_WRT_BOTH;
+  if (wrt & CVVDP_WRT_TEST) side(p.fir, p.chain.acc[0].d, "d", "carry", g_test, g_grad);
+  if (wrt & CVVDP_WRT_REFERENCE) side(p.fir_r, p.chain.acc_r[0].d, both ? "d_r" : "d", both ? "carry_r" : "carry", g_ref, g_grad_r);
+  if (both) REQUIRE(p.fir.carry != p.fir_r.carry, "block plan: the two sides share a carry");
   spans_disjoint();
 }
 static void chk_plan(const ParamPlan& p) {
@@ -364,7 +411,7 @@ static void chk_plan(const ParamPlan& p) {
 
 // One route of a scored case: nothing to do where the configured clip has no scratch size; a scratch one byte short must be refused;
 // with exactly the size, the plan is checked if the call is accepted (it is refused for the display, or for how the clip was scored).
-static long g_route[5], g_levels_seen[CVVDP_MAX_LEVELS + 1], g_fl_side[2], g_padding[2], g_cuts[4];
+static long g_route[5], g_route_wrt[4][4], g_levels_seen[CVVDP_MAX_LEVELS + 1], g_fl_side[2], g_padding[2], g_cuts[4];      // g_route_wrt[pixel route][CVVDP_WRT_*]
 template <class Plan, class Prepare, class Check>
 static bool grad_route(int route, cvvdp_handle* h, size_t need, Prepare prepare, Check check) {
   if (need == 0) return false;
@@ -380,40 +427,44 @@ static bool grad_route(int route, cvvdp_handle* h, size_t need, Prepare prepare,
 
 // The gradient entries after a clip was scored, in the order of the Python mirror: the image's or the one-block clip's gradient and the
 // parameters' gradient of the block processed last; then begin, and the clip's blocks once more with the two per-block entries after each.
-static void check_gradients(cvvdp_handle* h, const cvvdp_clip& c, const int64_t st[5], float* ws, size_t ws_bytes, const void* src, const std::vector<int32_t>& hs0) {
+// wrt: the sides the four pixel routes of this clip are asked for (CVVDP_WRT_*); a side wrt leaves out is handed in all the same and
+// must not show up in the plan.  The scratch sizes are the ones cvvdp_*_wrt_scratch_bytes hand out.
+static void check_gradients(cvvdp_handle* h, const cvvdp_clip& c, int32_t wrt, const int64_t st[5], float* ws, size_t ws_bytes, const void* src, const std::vector<int32_t>& hs0) {
   using namespace cvvdp;
   const size_t clip_floats = (size_t)c.batch * 3 * c.n_frames * c.height * c.width;
-  g_test.bytes = g_grad.bytes = clip_floats * sizeof(float);
+  g_test.bytes = g_grad.bytes = g_ref.bytes = g_grad_r.bytes = clip_floats * sizeof(float);
   g_dq.bytes = (size_t)c.batch * (c.is_video ? 4 : 3) * c.n_frames * c.n_levels * sizeof(float); g_acc.bytes = (size_t)c.batch * CVVDP_PARAM_GRAD_COUNT * sizeof(double);
   void* const sc = reinterpret_cast<void*>(g_scratch.lo);
-  const void* const test = reinterpret_cast<const void*>(g_test.lo);
-  float* const grad = reinterpret_cast<float*>(g_grad.lo);
+  const GradSides sd{wrt, reinterpret_cast<const void*>(g_test.lo), st, reinterpret_cast<float*>(g_grad.lo), st, g_grad.bytes,
+                     reinterpret_cast<const void*>(g_ref.lo), st, reinterpret_cast<float*>(g_grad_r.lo), st, g_grad_r.bytes};
+  auto pixel = [&](int route, bool ok) { g_route_wrt[route][wrt] += ok; return ok; };
   auto param = [&] {
     return grad_route<ParamPlan>(4, h, param_grad_scratch(h), [&](size_t n, ParamPlan& p) { return param_grad_prepare(h, reinterpret_cast<const float*>(g_dq.lo), reinterpret_cast<double*>(g_acc.lo), sc, n, p); },
                                  [](const ParamPlan& p) { chk_plan(p); });
   };
   auto block = [&] {
-    return grad_route<GradBlocksPlan>(3, h, grad_blocks_scratch(h), [&](size_t n, GradBlocksPlan& p) { return grad_blocks_block_prepare(h, test, st, grad, st, g_grad.bytes, sc, n, p); },
-                                      [](const GradBlocksPlan& p) { chk_plan_block(p); });
+    return pixel(3, grad_route<GradBlocksPlan>(3, h, grad_wrt_scratch(h, 2, wrt), [&](size_t n, GradBlocksPlan& p) { return grad_blocks_block_prepare(h, sd, sc, n, p); },
+                                               [&](const GradBlocksPlan& p) { REQUIRE(p.chain.wrt == wrt, "block plan: wrt"); chk_plan_block(p); }));
   };
   bool any = param();
   if (!c.is_video) {
-    any |= grad_route<GradPlan>(0, h, grad_scratch(h), [&](size_t n, GradPlan& p) { return grad_prepare(h, test, st, grad, st, g_grad.bytes, sc, n, p); }, [](const GradPlan& p) { chk_plan(p); });
+    any |= pixel(0, grad_route<GradPlan>(0, h, grad_wrt_scratch(h, 0, wrt), [&](size_t n, GradPlan& p) { return grad_prepare(h, sd, sc, n, p); },
+                                         [&](const GradPlan& p) { REQUIRE(p.chain.wrt == wrt, "image plan: wrt"); chk_plan(p); }));
     g_levels_seen[c.n_levels] += any;
     return;
   }
   const int M = c.filter_len - 1;
   bool replicate = true;
   for (int i = 0; i < M; ++i) replicate = replicate && hs0[i] == 0;
-  const bool one = grad_route<GradVideoPlan>(1, h, grad_video_scratch(h), [&](size_t n, GradVideoPlan& p) { return grad_video_prepare(h, test, st, grad, st, g_grad.bytes, sc, n, p); },
-                                             [](const GradVideoPlan& p) { chk_plan(p); });
-  const bool begun = grad_route<GradBlocksPlan>(2, h, grad_blocks_scratch(h), [&](size_t n, GradBlocksPlan& p) { return grad_blocks_begin_prepare(h, sc, n, p); },
-                                                [](const GradBlocksPlan& p) { chk_plan_begin(p); });
+  const bool one = pixel(1, grad_route<GradVideoPlan>(1, h, grad_wrt_scratch(h, 1, wrt), [&](size_t n, GradVideoPlan& p) { return grad_video_prepare(h, sd, sc, n, p); },
+                                                      [&](const GradVideoPlan& p) { REQUIRE(p.chain.wrt == wrt, "video plan: wrt"); chk_plan(p); }));
+  const bool begun = pixel(2, grad_route<GradBlocksPlan>(2, h, grad_wrt_scratch(h, 2, wrt), [&](size_t n, GradBlocksPlan& p) { return grad_blocks_begin_prepare(h, wrt, sc, n, p); },
+                                                         [&](const GradBlocksPlan& p) { chk_plan_begin(p, wrt); }));
   g_levels_seen[c.n_levels] += any || one || begun;
   if (one || begun) { ++g_fl_side[c.filter_len > CVVDP_GRAD_FIR_WL]; ++g_padding[replicate]; }
   if (!begun) return;
   REQUIRE(!block(), "a block's gradient was accepted before begin had run");
-  REQUIRE(grad_blocks_check_launch(h, false) == CVVDP_OK, "begin: %s", cvvdp_last_error(h));
+  REQUIRE(grad_blocks_after_launch(h, false) == CVVDP_OK, "begin: %s", cvvdp_last_error(h));
   REQUIRE(cvvdp_configure(h, &c) == CVVDP_OK && cvvdp_bind_workspace(h, ws, ws_bytes) == CVVDP_OK, "the second walk's configure: %s", cvvdp_last_error(h));
   int n_blocks = 0;
   for (int done = 0; done < c.n_frames; ++n_blocks) {
@@ -423,7 +474,7 @@ static void check_gradients(cvvdp_handle* h, const cvvdp_clip& c, const int64_t 
     REQUIRE(cvvdp_process_block(h, src, src, CVVDP_F32, st, st, 0, hs.data(), n, done, nullptr) == CVVDP_OK, "the second walk's block at %d: %s", done, cvvdp_last_error(h));
     (void)param();
     REQUIRE(block(), "the gradient of the block at frame %d was refused: %s", done, cvvdp_last_error(h));
-    REQUIRE(grad_blocks_check_launch(h, true) == CVVDP_OK, "block: %s", cvvdp_last_error(h));
+    REQUIRE(grad_blocks_after_launch(h, true) == CVVDP_OK, "block: %s", cvvdp_last_error(h));
     REQUIRE(!block(), "the block at frame %d was accepted twice", done);
     done += n;
   }
@@ -605,7 +656,7 @@ int main(int argc, char** argv) {
       (void)cvvdp_profile_read(h, ms, cnt);
       (void)cvvdp_profile_enable(h, 0);
       for (int w = 0; w <= CVVDP_BUF_Q; ++w) { void* ptr = nullptr; size_t nf = 0; if (cvvdp_debug_buffer(h, w, 0, &ptr, &nf) == CVVDP_OK) in_ws(ptr, nf, "debug buffer"); }
-      check_gradients(h, c, st, fake_ws, bytes, fake_src, hs0);
+      check_gradients(h, c, ri(CVVDP_WRT_TEST, CVVDP_WRT_BOTH), st, fake_ws, bytes, fake_src, hs0);
       ++ran;
     }
     cvvdp_destroy(h);
@@ -615,6 +666,14 @@ int main(int argc, char** argv) {
   REQUIRE(cvvdp_configure(nullptr, nullptr) != CVVDP_OK && cvvdp_workspace_bytes(nullptr) == 0, "null handle accepted");
   cvvdp_destroy(nullptr);
   printf("host_sanitize: gradient plans checked: image %ld, video %ld, begin %ld, block %ld, param %ld\n", g_route[0], g_route[1], g_route[2], g_route[3], g_route[4]);
+  printf("host_sanitize: ... per pixel route and wrt:");
+  {
+    const char* const route[4] = {"image", "video", "begin", "block"};
+    const char* const side[4] = {"", "test", "reference", "both"};
+    for (int r = 0; r < 4; ++r)
+      for (int w = CVVDP_WRT_TEST; w <= CVVDP_WRT_BOTH; ++w) printf(" %s/%s %ld", route[r], side[w], g_route_wrt[r][w]);
+  }
+  printf("\n");
   printf("host_sanitize: ... of 1 .. %d levels:", CVVDP_MAX_LEVELS);
   for (int l = 1; l <= CVVDP_MAX_LEVELS; ++l) printf(" %ld", g_levels_seen[l]);
   printf("\n");

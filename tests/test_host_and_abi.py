@@ -160,8 +160,12 @@ def test_product_library_has_no_development_knobs_and_the_binding_loads_only_it(
     import sys
     from colorvideovdp_amd import _capi
     assert _capi.lib().cvvdp_build_flags() & _capi.BUILD_DEV_KNOBS == 0
-    src = open(os.path.join(ROOT, "colorvideovdp_amd", "csrc", "core.cpp")).read()
-    assert "getenv" not in src                                   # every knob goes through kernels.h::dev_knob
+    import glob
+    csrc = os.path.join(ROOT, "colorvideovdp_amd", "csrc")
+    host = sorted(glob.glob(os.path.join(csrc, "*.cpp"))) + [os.path.join(csrc, "handle.h")]
+    assert {"core.cpp", "score_host.cpp", "pixel_host.cpp", "grad_host.cpp", "dump_host.cpp"} <= {os.path.basename(f) for f in host}
+    for f in host:
+        assert "getenv" not in open(f).read(), f                 # every knob goes through kernels.h::dev_knob
     code = "from colorvideovdp_amd import _capi; print(_capi.LIB_PATH)"
     env = dict(os.environ, CVVDP_LIB=str(tmp_path / "other.so"), PYTHONPATH=ROOT)
     env.pop("CVVDP_DEV_KNOBS", None)
