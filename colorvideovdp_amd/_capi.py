@@ -225,6 +225,13 @@ SYMBOLS = {
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                               C.c_void_p, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_pixel_psnr_gradient_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    # (handle, wrt, test, strides, reference, strides, B, C, n_frames, H, W, args, mse_acc, grad, strides, bytes, grad_ref, strides, bytes,
+    #  stream)
+    "cvvdp_pixel_psnr_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PsnrArgs), C.c_void_p,
+                                            C.c_void_p, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p, C.POINTER(C.c_int64), C.c_size_t,
+                                            C.c_void_p]),
     "cvvdp_preview_args_size": (C.c_int32, []),
     "cvvdp_pixel_preview": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(YuvFormat), C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(PreviewArgs), C.c_void_p, C.c_size_t, C.c_void_p]),

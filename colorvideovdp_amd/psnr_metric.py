@@ -23,6 +23,7 @@ import torch
 from . import _capi
 from ._frames import batch_strides, yuv_block_resized
 from .display_model import vvdp_display_photo_eotf, vvdp_display_photometry
+from .psnr_grad import psnr_gradient
 from .video_source import video_source, video_source_array
 from .vq_metric import register_metric, vq_metric
 
@@ -65,8 +66,9 @@ def psnr_scalars(dm):
     return out
 
 
-class _psnr_base(vq_metric):
-    """Shared machinery; the subclasses fix the colour space the frames are compared in."""
+class _psnr_base(psnr_gradient, vq_metric):
+    """Shared machinery; the subclasses fix the colour space the frames are compared in.  predict_with_gradient and differentiable_loss
+    of the three PSNR metrics: psnr_grad.py."""
 
     metric_colorspace = None
 
@@ -261,6 +263,7 @@ class psnr_rgb(_psnr_base):
     display is linear or PQ (display_model.py:206-226); max_I = 1."""
 
     metric_colorspace = "display_encoded_100nit"
+    _psnr_loss = True
 
     def __init__(self, display_name="standard_4k", display_photometry=None, device=None, config_paths=[]):
         self._setup(display_name, display_photometry, device, config_paths)
@@ -274,6 +277,7 @@ class pu_psnr_y(_psnr_base):
     of the unencoded luminance, as in the reference."""
 
     metric_colorspace = "Y"
+    _psnr_loss = True
 
     def __init__(self, display_name="standard_4k", display_photometry=None, color_space="sRGB", device=None, config_paths=[]):
         self.color_space = color_space  # input content colour space (stored, as in the reference)

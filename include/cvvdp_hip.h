@@ -667,6 +667,35 @@ int cvvdp_pixel_msssim_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_t
                                 float* dev_grad_ref, const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* dev_scratch,
                                 size_t scratch_bytes, void* stream);
 
+/* Gradient of the PSNR metrics in the frames (csrc/psnr_grad.hip, csrc/psnr_grad_dev.h): d psnr[b] / d test, d psnr[b] /
+ * d reference or both, where psnr[b] = 20 log10(max_I) - 10 log10(mse_acc[b] / N) is the score the caller forms from the mse_acc that
+ * cvvdp_pixel_sse accumulated over the WHOLE clip.  A block of n_frames frames of the clip is handed in; the clip's length N cancels.
+ *   wrt                CVVDP_WRT_TEST, CVVDP_WRT_REFERENCE or CVVDP_WRT_BOTH; anything else is CVVDP_E_ARG
+ *   dev_test, dev_ref  float32 [B, 3, n_frames, H, W] with non-negative element strides, as cvvdp_pixel_sse takes them with CVVDP_F32;
+ *                      C must be 3
+ *   args               the forward's arguments, every target.  CVVDP_PSNR_AS_IS: Jacobian 1, no clamp.  CVVDP_PSNR_PU21: the slope of
+ *                      PU21(forward(V)) / pu_norm on linear and PQ displays (CVVDP_E_UNSUPPORTED on the others, which the metrics never
+ *                      ask for).  CVVDP_PSNR_Y, CVVDP_PSNR_RGB2020: rows transposed, through the display model of every EOTF (on HLG
+ *                      the OOTF couples the three channels)
+ *   dev_mse_acc        double [B], 8-byte aligned: what cvvdp_pixel_sse left after the clip's last block, on the same stream.  The factor
+ *                      k_b = -(20 / ln 10) / (mse_acc[b] n_out H W) is formed on the device in double; mse_acc[b] = 0 (identical
+ *                      frames, psnr = +inf) gives an all-zero gradient
+ *   dev_grad_*         float32, written at strides_grad_* (elements, non-negative, [B, 3, n_frames, H, W]); the last element must lie
+ *                      inside grad_*_bytes.  Only the sides wrt names are read and written
+ * The reference side is -k_b (o_T - o_R) through the Jacobian of the reference's own samples.  Conventions: torch's subgradient
+ * rules (a clamp passes at its bounds and gives 0 outside); 0 where the reference's autograd gives NaN or infinity (a PQ sample of
+ * exactly 0, an HLG pixel whose scene luminance is 0, a product that is not finite).  One streaming pass, pointwise: no atomics, no
+ * scratch (cvvdp_pixel_psnr_gradient_scratch_bytes answers 0 and exists for symmetry), the same bits on every run and for every cut
+ * of a clip into blocks.  Nothing synchronises.  Null or misaligned pointers, negative strides, C != 3, a bad geometry, a short
+ * gradient buffer, an unknown wrt or target give CVVDP_E_ARG -- all before any launch.  Added; nothing else changed, so
+ * CVVDP_ABI_VERSION stays 14. */
+size_t cvvdp_pixel_psnr_gradient_scratch_bytes(int32_t wrt, int32_t B, int32_t n_frames, int32_t H, int32_t W);
+int cvvdp_pixel_psnr_gradient(cvvdp_handle* h, int32_t wrt, const float* dev_test, const int64_t strides_test[5], const float* dev_ref,
+                              const int64_t strides_ref[5], int32_t B, int32_t C, int32_t n_frames, int32_t H, int32_t W,
+                              const cvvdp_psnr_args* args, const double* dev_mse_acc, float* dev_grad_test,
+                              const int64_t strides_grad_test[5], size_t grad_test_bytes, float* dev_grad_ref,
+                              const int64_t strides_grad_ref[5], size_t grad_ref_bytes, void* stream);
+
 /* Display-model preview (pycvvdp/dm_preview_metric.py): n_frames frames of ONE side, from raw samples to a named colour space, packed
  * for a file writer, in one pass.  The source arguments are those of one side of cvvdp_pixel_sse (dev_src with dtype and strides, or
  * planar Y'CbCr with yuv; is_ref picks frame_stride_ref instead of frame_stride_test), B must be 1.  Per pixel: the handle's display
