@@ -12,6 +12,12 @@ parameters, their gradient and the optimiser's state on the device.  Naming a ba
 `--parameters` switches `fit` to rescoring mode: the clips are scored again on every step with
 predict_video_source_with_parameter_gradient(), which is the full fit the reference ships no script for.
 
+`-m cvvdp-ml-saliency` calibrates the ML head instead: `extract` writes the per-cell features of every row as
+`<id>_mlfeat.npz`, and `fit` runs Adam on the packed weights of both MLPs (and on the model's scalar baseband_weight when `--parameters
+baseband_weight` names it) through cvvdp_ml_saliency.differentiable_jods, whose backward is cvvdp_ml_saliency_head_grad.  It writes
+OUT/cvvdp_ml_saliency/cvvdp.ckpt and cvvdp_parameters.json, which cvvdp_ml_saliency(config_paths=[OUT]) loads.  Deviation D2 from the
+reference's training: no dropout (its MLPs carry Dropout(0.2) in training mode); the fit is deterministic.
+
 Only the standard library, numpy and torch are used.  Deviation D1 from train.py: the mini-batch order is
 numpy.random.default_rng(seed + epoch).permutation, not the DataLoader's; with -b at or above the size of the training set the two
 agree up to the order of summation.  DESIGN.md 7j has the layout, the summation order and what stays out."""
@@ -624,6 +630,163 @@ def fit_rescoring(metric, train_rows, args, names, steps=None):
             "theta": theta.detach().cpu().numpy(), "band": band.detach().cpu().numpy()}
 
 
+# ---------------------------------------------------------------- the ML head (-m cvvdp-ml-saliency)
+ML_MODEL = "cvvdp_ml_saliency"
+
+
+def _ml_metric(args, random_init):
+    from .cvvdp_ml_metric import cvvdp_ml_saliency
+    display = args.display if args.display not in (None, "per-row") else "standard_4k"
+    return cvvdp_ml_saliency(quiet=True, display_name=display, temp_padding="replicate", config_paths=args.config_paths, random_init=random_init)
+
+
+def write_ml_features(fname, features, frames_per_second):
+    """`band<k>` [F, H', W', C, 6] float32 of one clip (features: the list extract_features returns, batch 1), and its frame rate."""
+    arrays = {}
+    for k, f in enumerate(features):
+        f = f.detach().cpu().numpy() if torch.is_tensor(f) else np.asarray(f)
+        if f.ndim != 6 or f.shape[0] != 1 or f.shape[5] != 6:
+            raise vq_exception(f"features of band {k} have shape {f.shape}, expected [1, F, H', W', C, 6]")
+        arrays[f"band{k}"] = np.ascontiguousarray(f[0], dtype=np.float32)
+    np.savez(fname, bands=np.int32(len(arrays)), frames_per_second=np.float64(frames_per_second), **arrays)
+
+
+def read_ml_features(fname, device=None):
+    """The list of [1, F, H', W', C, 6] float32 tensors write_ml_features stored."""
+    if not os.path.isfile(fname):
+        raise vq_exception(f'Features missing: "{fname}" (run `extract -m cvvdp-ml-saliency` first)')
+    with np.load(fname, allow_pickle=False) as g:
+        feats = [torch.from_numpy(g[f"band{k}"][None]) for k in range(int(g["bands"]))]
+    return [f.to(device) for f in feats] if device is not None else feats
+
+
+def write_ml_model(metric, output_dir, weights, baseband_weight, comment=None):
+    """OUTPUT_DIR/cvvdp_ml_saliency/cvvdp.ckpt ({"state_dict": the networks of the packed `weights`}) and cvvdp_parameters.json (the
+    metric's own parameter file with `baseband_weight` replaced), the layout cvvdp_ml_saliency(config_paths=[OUTPUT_DIR]) loads.
+    Returns the directory."""
+    from .config import json2dict
+    from .cvvdp_ml_metric import unpack_weights
+    out = os.path.join(output_dir, ML_MODEL)
+    os.makedirs(out, exist_ok=True)
+    torch.save({"state_dict": unpack_weights(weights, state_dict=True)}, os.path.join(out, "cvvdp.ckpt"))
+    p = dict(json2dict(metric.parameters_file))
+    p["baseband_weight"] = float(np.float32(baseband_weight))
+    if comment:
+        p["__comment"] = comment
+    with open(os.path.join(out, "cvvdp_parameters.json"), "w") as f:
+        json.dump(p, f, indent=4)
+        f.write("\n")
+    return out
+
+
+def fit_ml(metric, train, val, fit_baseband=False, batch=4, learning_rate=1e-3, num_epochs=50, val_epoch=1, save="latest", seed=0,
+           log_dir=None):
+    """Adam on the mean squared error of the JOD over the packed weights of the metric's networks (and its baseband_weight), on stored
+    features.  train, val: (list of feature lists, targets); val may be None.  Every clip of a mini-batch is one
+    differentiable_jods() (forward head, and the HIP weight gradient in backward()).  Returns a dict: weights (float32 [ML_WEIGHTS],
+    per --save), baseband_weight, epoch, losses (one per step), validation, jod_train (of the returned model)."""
+    if batch < 1 or num_epochs < 0 or val_epoch < 1:
+        raise vq_exception("fit: batch and val-epoch must be at least 1, num-epochs at least 0")
+    keeper = _Keeper(save)
+    dev = metric.device
+    feats, targets = train
+    if not feats:
+        raise vq_exception("fit: the training split is empty")
+    target = torch.as_tensor(np.asarray(targets, dtype=np.float32)).to(dev)
+    w = metric.weight_tensor().requires_grad_(True)
+    bw = torch.tensor(float(metric._ml_baseband_weight), dtype=torch.float32, device=dev, requires_grad=fit_baseband)
+    opt = torch.optim.Adam([w, bw] if fit_baseband else [w], lr=learning_rate)
+    log = _Log(log_dir)
+    losses, validation = [], []
+
+    def jods(clips):
+        with torch.no_grad():
+            return torch.cat([metric._head_forward(c, metric._weights_arg(w), float(bw)).reshape(-1)[:1] for c in clips])
+
+    def state():
+        return w.detach().clone(), float(bw.detach())
+
+    def validate(epoch):
+        if val is None:
+            return
+        score = measures(jods(val[0]).cpu().numpy(), val[1])
+        validation.append((epoch, score))
+        log.validation(epoch, score)
+        logging.info(f"epoch {epoch}: validation rmse {score['rmse']:.4f} pearson {score['pearson']:.4f} spearman {score['spearman']:.4f}")
+        keeper.offer(epoch, score, state)
+
+    try:
+        validate(-1)
+        done, epoch = 0, -1
+        for epoch in range(num_epochs):
+            perm, cuts = _batches(len(feats), batch, seed, epoch)
+            for a, b in cuts:
+                opt.zero_grad(set_to_none=True)
+                q = torch.cat([metric.differentiable_jods(feats[k], w, bw if fit_baseband else None).reshape(-1)[:1] for k in perm[a:b]])
+                loss = ((q - target[torch.from_numpy(perm[a:b].astype(np.int64)).to(dev)]) ** 2).mean()
+                loss.backward()
+                opt.step()
+                losses.append(float(loss.detach().cpu()))
+                log.loss(epoch, done, losses[-1])
+                done += 1
+            if epoch % val_epoch == 0:
+                validate(epoch)
+    finally:
+        log.close()
+    if keeper.monitor is None or keeper.state is None:
+        (weights, bw_out), chosen_epoch = state(), epoch
+    else:
+        (weights, bw_out), chosen_epoch = keeper.state, keeper.epoch
+    with torch.no_grad():
+        jod_train = torch.cat([metric._head_forward(c, metric._weights_arg(weights), bw_out).reshape(-1)[:1] for c in feats]).cpu().numpy()
+    return {"weights": weights, "baseband_weight": bw_out, "epoch": chosen_epoch, "losses": losses, "validation": validation,
+            "jod_train": jod_train}
+
+
+def run_fit_ml(args, columns, rows, metric=None):
+    """`fit -m cvvdp-ml-saliency`.  Returns (the result of fit_ml, the directory written)."""
+    names = list(args.parameters or [])
+    for n in names:
+        if n != "baseband_weight":
+            raise vq_exception(f"unknown parameter '{n}': with -m cvvdp-ml-saliency the networks are always fitted and --parameters may add baseband_weight")
+    if args.split_column not in columns:
+        raise vq_exception(f'Split column "{args.split_column}" not found')
+    if "jod" not in columns:
+        raise vq_exception("the table has no column 'jod'")
+    if args.batch < 1:
+        raise vq_exception("--batch must be at least 1")
+    _Keeper(args.save)
+    train_rows, test_rows = split_rows(rows, args.split_column, args.seed, args.train_ratio)
+    if not train_rows:
+        raise vq_exception("fit: the training split is empty")
+    if metric is None:
+        if args.ckpt is not None and not os.path.isfile(args.ckpt):
+            raise vq_exception(f"--ckpt {args.ckpt}: no such file")
+        with torch.random.fork_rng(devices=[]):                          # a seeded start that leaves the caller's generator alone
+            torch.manual_seed(args.seed)
+            metric = _ml_metric(args, random_init=True)
+        if args.ckpt is not None:
+            metric.load_state_dict_nets(torch.load(args.ckpt, map_location="cpu")["state_dict"])
+    if not torch.cuda.is_available():
+        raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
+    ft_path = features_dir(args.features_suffix)
+
+    def load(rows_, split):
+        if not rows_:
+            return None
+        return ([read_ml_features(os.path.join(ft_path, split, row_id(r["test"]) + "_mlfeat.npz"), metric.device) for r in rows_],
+                [float(r["jod"]) for r in rows_])
+
+    result = fit_ml(metric, load(train_rows, "train"), load(test_rows, "test"), fit_baseband="baseband_weight" in names, batch=args.batch,
+                    learning_rate=args.learning_rate, num_epochs=args.num_epochs, val_epoch=args.val_epoch, save=args.save, seed=args.seed,
+                    log_dir=args.log_dir)
+    comment = (f"ColorVideoVDP-ML-Saliency parameters generated by the calibration tool. The networks in cvvdp.ckpt are fit on data from file "
+               f"{args.quality_file} (epoch {result['epoch']}).")
+    out = write_ml_model(metric, args.output_dir, result["weights"], result["baseband_weight"], comment)
+    logging.info(f'New ColorVideoVDP-ML-Saliency checkpoint and parameters saved in "{out}"')
+    return result, out
+
+
 # ---------------------------------------------------------------- command line
 def _common(p):
     p.add_argument("quality_file", help="Path to the .csv file with the quality scores.")
@@ -639,6 +802,8 @@ def _common(p):
     p.add_argument("--full-screen-resize", choices=["bilinear", "bicubic", "nearest", "area"], default=None)
     p.add_argument("--fps", type=float, default=None, help="Frames per second of .npy clips (files that carry a rate ignore it).")
     p.add_argument("-v", "--verbose", action="store_true", default=False)
+    p.add_argument("-m", "--metric", choices=["cvvdp", "cvvdp-ml-saliency"], default="cvvdp",
+                   help="The model to calibrate: the base model's parameters, or the networks of the ML head (needs -c with its parameter file).")
 
 
 def make_parser():
@@ -660,6 +825,7 @@ def make_parser():
     ft.add_argument("--parameters", nargs="+", default=None,
                     help=f"Parameters to fit (default: {' '.join(DEFAULT_PARAMETERS)}; image_int may be added; any of {' '.join(BAND_PARAMETERS)} selects rescoring mode).")
     ft.add_argument("--resample-bands", action="store_true", default=False, help="Refused.")
+    ft.add_argument("--ckpt", default=None, help="-m cvvdp-ml-saliency: the checkpoint to start from (default: a random initialisation seeded with --seed).")
     return parser
 
 
@@ -681,6 +847,7 @@ def parse_arguments(argv):
 def run_extract(args, columns, rows, metric=None):
     """extract_features.py:79-151.  Returns the files written."""
     from .cvvdp_metric import cvvdp
+    ml = getattr(args, "metric", "cvvdp") == "cvvdp-ml-saliency"
     if args.display is None:
         raise vq_exception('Please select a display name (-d), or include a column titled "display" and pass "--display per-row".')
     if args.display == "per-row" and "display" not in columns:
@@ -696,6 +863,9 @@ def run_extract(args, columns, rows, metric=None):
         logging.info(f"Worker {start + 1} out of {step} workers.")
     train_cond = set(split_conditions([r[args.split_column] for r in rows], args.seed, args.train_ratio)[0])
     ft_path = features_dir(args.features_suffix)
+    if metric is None and ml:
+        with torch.random.fork_rng(devices=[]):                      # (the features do not depend on the networks, and the caller's
+            metric = _ml_metric(args, random_init=True)              # generator is not the one to draw them from)
     if metric is None:
         metric = cvvdp(quiet=True, display_name="standard_4k" if args.display == "per-row" else args.display, temp_padding="replicate",
                        config_paths=args.config_paths)
@@ -705,18 +875,24 @@ def run_extract(args, columns, rows, metric=None):
     for kk in range(start, len(rows), step):
         row = rows[kk]
         rid = row_id(row["test"])
-        dest = os.path.join(ft_path, "train" if row[args.split_column] in train_cond else "test", rid + "_fmap.json")
+        dest = os.path.join(ft_path, "train" if row[args.split_column] in train_cond else "test", rid + ("_mlfeat.npz" if ml else "_fmap.json"))
         if args.resume and os.path.isfile(dest):
             logging.info(f"Skipping condition {rid}")
             continue
         photo, geom = _set_display(metric, _row_display(row, args), args.config_paths)
         try:
             with torch.no_grad():
-                _, stats = metric.predict_video_source(_source(row, args, photo, geom))
+                if ml:
+                    vs, _, feats = metric._source_features(_source(row, args, photo, geom))
+                else:
+                    _, stats = metric.predict_video_source(_source(row, args, photo, geom))
         except Exception:
             logging.error(f"Failed on condition {rid}")
             raise
-        metric.write_features_to_json(stats, dest)
+        if ml:
+            write_ml_features(dest, feats, vs.get_frames_per_second())
+        else:
+            metric.write_features_to_json(stats, dest)
         written.append(dest)
     return written
 
@@ -735,6 +911,8 @@ def _feature_set(rows, split, args, device):
 def run_fit(args, columns, rows, metric=None):
     """train.py:60-169.  Returns (the result of the fit, the parameter file written)."""
     from .cvvdp_metric import cvvdp
+    if getattr(args, "metric", "cvvdp") == "cvvdp-ml-saliency":
+        return run_fit_ml(args, columns, rows, metric)
     pool_names, band_names = parameter_names(args.parameters)
     if args.split_column not in columns:
         raise vq_exception(f'Split column "{args.split_column}" not found')

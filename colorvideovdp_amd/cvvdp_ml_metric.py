@@ -17,7 +17,13 @@ This package ships neither and fetches nothing: the directory that holds both is
 command line).  A sub-directory of a configuration directory with the model's name is looked into first, so the parent of the
 reference's layout works as well.
 
-Not available: heat maps, distograms, frame sharding, `RegressionTransformer.get_heatmap`, training.
+Training of cvvdp_ml_saliency: the gradient of Q_JOD in the packed weights of both MLPs and in `baseband_weight` comes from one more HIP
+pass per band (cvvdp_ml_saliency_head_grad; csrc/ml_head_grad.hip): do_pooling_and_jods_with_weight_gradient,
+differentiable_jods (autograd), predict_with_weight_gradient; `calibration fit -m cvvdp-ml-saliency` runs Adam on them and writes a
+cvvdp.ckpt.  No dropout: the reference's MLPs carry Dropout(0.2) in training mode, the fit here is deterministic.
+
+Not available: heat maps, distograms, frame sharding, `RegressionTransformer.get_heatmap`, training of the transformer head, the
+gradient in the features or pixels.
 """
 import ctypes
 import logging
@@ -30,7 +36,7 @@ from . import _capi
 from . import host_setup as hs
 from .config import config_files, json2dict
 from .cvvdp_metric import cvvdp
-from .video_source import video_source
+from .video_source import video_source, video_source_array
 from .vq_metric import register_metric, vq_exception
 
 f32 = np.float32
@@ -93,6 +99,59 @@ def pack_weights(nets):
         flat = np.concatenate([np.concatenate([w.numpy().reshape(-1), b.numpy().reshape(-1)]) for w, b in nets[net]]).astype(f32)
         out[start:start + flat.size] = flat
     return out
+
+
+def _layer_slices():
+    """[(net, layer, weight slice, (out, in), bias slice)] of the packed buffer."""
+    out = []
+    for net, start in (("att_net", 0), ("feature_net", _capi.ML_FEATURE_NET_OFFSET)):
+        dims, pos = ARCHITECTURE[net], start
+        for k in range(len(dims) - 1):
+            nw, nb = dims[k] * dims[k + 1], dims[k + 1]
+            out.append((net, k, slice(pos, pos + nw), (dims[k + 1], dims[k]), slice(pos + nw, pos + nw + nb)))
+            pos += nw + nb
+    return out
+
+
+def _nets_as_state_dict(nets):
+    """{'att_net': [(weight, bias), ...], ...} under torchvision's layer indices (0, 3, 6, ...): `<net>.<3 k>.weight` / `.bias`."""
+    return {f"{net}.{3 * k}.{kind}": t for net, layers in nets.items() for k, wb in enumerate(layers) for kind, t in zip(("weight", "bias"), wb)}
+
+
+def unpack_weights(packed, state_dict=False):
+    """The inverse of pack_weights: {'att_net': [(weight, bias), ...], 'feature_net': [...]} as float32 CPU tensors from a packed buffer
+    (array or tensor, ML_WEIGHTS values; the padding is dropped), or with state_dict=True the same as a state dict with torchvision's
+    layer indices (0, 3, 6, ...), what a checkpoint's `state_dict` holds.  load_state_dict_nets() takes either."""
+    a = packed.detach().cpu().numpy() if torch.is_tensor(packed) else np.asarray(packed)
+    a = np.ascontiguousarray(a, dtype=f32).reshape(-1)
+    if a.size != _capi.ML_WEIGHTS:
+        raise ValueError(f"unpack_weights: {a.size} values, the packed head has {_capi.ML_WEIGHTS}")
+    nets = {net: [] for net in ARCHITECTURE}
+    for net, _, sw, shape, sb in _layer_slices():
+        nets[net].append((torch.from_numpy(a[sw].reshape(shape).copy()), torch.from_numpy(a[sb].copy())))
+    return _nets_as_state_dict(nets) if state_dict else nets
+
+
+class _HeadJods(torch.autograd.Function):
+    """Q_JOD [B] of cvvdp_ml_saliency attached to autograd in the packed weights and (optionally) a scalar baseband_weight."""
+
+    @staticmethod
+    def forward(ctx, metric, features, weights, baseband_weight):
+        bw = None if baseband_weight is None else float(baseband_weight.detach())
+        ctx.metric, ctx.features, ctx.bw = metric, features, bw
+        ctx.save_for_backward(weights, *(() if baseband_weight is None else (baseband_weight,)))
+        return metric._head_forward(features, metric._weights_arg(weights), bw)
+
+    @staticmethod
+    def backward(ctx, grad_q):
+        saved = ctx.saved_tensors
+        g, g_bw = ctx.metric._head_weight_gradient(ctx.features, grad_q, ctx.metric._weights_arg(saved[0]), ctx.bw)
+        g = g.to(saved[0].device, saved[0].dtype).reshape(saved[0].shape) if ctx.needs_input_grad[2] else None
+        if len(saved) > 1 and ctx.needs_input_grad[3]:
+            g_bw = g_bw.to(saved[1].device, saved[1].dtype).reshape(saved[1].shape)
+        else:
+            g_bw = None
+        return None, None, g, g_bw
 
 
 class _cvvdp_ml(cvvdp):
@@ -165,8 +224,9 @@ class _cvvdp_ml(cvvdp):
         self._shard = None
 
     # ------------------------------------------------------------------ public API
-    def predict_video_source(self, vid_source):
-        """cvvdp_ml_base.predict_video_source (cvvdp_ml_metric.py:174-201)."""
+    def _score_source(self, vid_source, head):
+        """(the source itself, its size, head(features)) of what predict_video_source scores: the refusals, the display-model swap of a raw
+        source, extract_features, and `head` on the features before the swap is undone."""
         inner = getattr(vid_source, "vs", None)
         if isinstance(inner, video_source):
             vid_source = inner
@@ -174,7 +234,7 @@ class _cvvdp_ml(cvvdp):
             raise vq_exception("--temp-resample sources are scored by the cvvdp metric only")
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
-        height, width, N_frames = vid_source.get_video_size()
+        size = vid_source.get_video_size()
         # a raw source that carries its own display photometry is measured with it, as in cvvdp.predict_video_source
         src_dm = getattr(vid_source, "dm_photometry", None)
         swap = src_dm is not None and src_dm is not self.display_photometry and self._is_raw_source(vid_source)
@@ -184,23 +244,37 @@ class _cvvdp_ml(cvvdp):
             self._make_handle()
         try:
             features, _ = self.extract_features(vid_source)
-            Q_jod = self.do_pooling_and_jods(features)
+            out = head(features)
         finally:
             if swap:
                 self.display_photometry = prev
                 self._make_handle()
+        return vid_source, size, out
+
+    def _source_features(self, vid_source):
+        """(the source itself, its size, the features) of what predict_video_source scores."""
+        return self._score_source(vid_source, lambda features: features)
+
+    def _source_stats(self, vid_source, size):
+        height, width, N_frames = size
         pyr_height, freqs = hs.band_frequencies(width, height, self.pix_per_deg)
         rho_band = freqs.copy()
         rho_band[pyr_height] = 0.1
-        stats = {"rho_band": rho_band, "frames_per_second": vid_source.get_frames_per_second(), "width": width, "height": height,
-                 "N_frames": N_frames}
-        return (Q_jod.squeeze(), stats)
+        return {"rho_band": rho_band, "frames_per_second": vid_source.get_frames_per_second(), "width": width, "height": height,
+                "N_frames": N_frames}
 
-    def _check_features(self, features):
+    def predict_video_source(self, vid_source):
+        """cvvdp_ml_base.predict_video_source (cvvdp_ml_metric.py:174-201)."""
+        vid_source, size, Q_jod = self._score_source(vid_source, self.do_pooling_and_jods)
+        return (Q_jod.squeeze(), self._source_stats(vid_source, size))
+
+    def _check_features(self, features, baseband_weight=None):
         """B, C and an iterator over the bands (the features as a contiguous fp32 device tensor, the head's scale: 1 / bands, times the model's
-        baseband_weight on the last band, times image_int for an image) of a list of [B, F, H', W', C, 6] tensors."""
+        baseband_weight on the last band, times image_int for an image) of a list of [B, F, H', W', C, 6] tensors.  baseband_weight: a
+        value in place of the model's."""
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
+        bw = float(self._ml_baseband_weight if baseband_weight is None else f32(baseband_weight))
         no_bands = len(features)
         if no_bands < 1:
             raise ValueError("do_pooling_and_jods: no bands")
@@ -213,7 +287,7 @@ class _cvvdp_ml(cvvdp):
                     raise ValueError(f"features[{bb}] has shape {tuple(f.shape)}, expected [{B}, F, H', W', {C}, 6]")
                 scale = 1.0 / no_bands
                 if bb == no_bands - 1:
-                    scale *= float(self._ml_baseband_weight)
+                    scale *= bw
                 if C == 3:
                     scale *= float(f32(self.parameters["image_int"]))
                 yield f, scale
@@ -238,13 +312,15 @@ class cvvdp_ml_saliency(_cvvdp_ml):
 
     def load_state_dict_nets(self, state_dict):
         """Replace both networks from a state dict with `att_net.<i>.weight` / `.bias` and `feature_net.<i>.weight` / `.bias` entries
-        (what a checkpoint's `state_dict` holds); validated like a checkpoint, and nothing changes if it does not validate."""
+        (what a checkpoint's `state_dict` holds), or from the nets unpack_weights() returns; validated like a checkpoint, and nothing
+        changes if it does not validate."""
+        if set(state_dict) == set(ARCHITECTURE):
+            state_dict = _nets_as_state_dict(state_dict)
         self._set_nets(nets_from_state_dict(state_dict))
 
     def state_dict_nets(self):
         """The networks as a state dict with torchvision's layer indices (0, 3, 6, ...)."""
-        return {f"{net}.{3 * k}.{kind}": t.clone() for net, layers in self._nets.items() for k, wb in enumerate(layers)
-                for kind, t in zip(("weight", "bias"), wb)}
+        return {key: t.clone() for key, t in _nets_as_state_dict(self._nets).items()}
 
     def packed_weights(self):
         """float32 [ML_WEIGHTS]: the buffer the kernel reads (pack_weights)."""
@@ -254,9 +330,24 @@ class cvvdp_ml_saliency(_cvvdp_ml):
         """cvvdp_ml_saliency.do_pooling_and_jods (cvvdp_ml_metric.py:496-541): features[band] is [B, F, H', W', C, 6] (any list of such
         tensors; C = 3 marks an image) -> Q_JOD[B] on the device.  One cvvdp_ml_saliency_head call per band; unlike the reference's,
         this one leaves the caller's tensors as they are."""
-        B, C, bands = self._check_features(features)
-        if self._weights_dev is None:
-            self._weights_dev = torch.from_numpy(self._packed).to(self.device)
+        return self._head_forward(features, self._weights_arg(None))
+
+    def _weights_arg(self, weights):
+        """The packed weights the kernels read: the metric's own (None), or a float32 tensor of ML_WEIGHTS values, moved to the device
+        and a 16-byte aligned contiguous buffer if it is not there already."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
+        if weights is None:
+            if self._weights_dev is None:
+                self._weights_dev = torch.from_numpy(self._packed).to(self.device)
+            return self._weights_dev
+        if not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.numel() != _capi.ML_WEIGHTS:
+            raise ValueError(f"weights must be a float32 tensor of {_capi.ML_WEIGHTS} values (weight_tensor())")
+        w = weights.detach().to(self.device).contiguous().reshape(-1)
+        return w.clone() if w.data_ptr() % 16 else w
+
+    def _head_forward(self, features, wdev, baseband_weight=None):
+        B, C, bands = self._check_features(features, baseband_weight)
         mask = sum(1 << s for s in set(self.disabled_features or ()))
         lib = _capi.lib()
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -268,10 +359,80 @@ class cvvdp_ml_saliency(_cvvdp_ml):
                 _, F, Hc, Wc = (int(n) for n in f.shape[:4])
                 nbytes = lib.cvvdp_ml_saliency_head_scratch_bytes(B, F, Hc, Wc)
                 scratch = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
-                rc = lib.cvvdp_ml_saliency_head(self._handle, f.data_ptr(), B, F, Hc, Wc, C, self._weights_dev.data_ptr(), scale, mask,
+                rc = lib.cvvdp_ml_saliency_head(self._handle, f.data_ptr(), B, F, Hc, Wc, C, wdev.data_ptr(), scale, mask,
                                                 Q.data_ptr(), scratch.data_ptr(), nbytes, stream)
                 _capi.check(self._handle, rc, "cvvdp_ml_saliency_head")
         return Q
+
+    # ------------------------------------------------------------------ training
+    def weight_tensor(self):
+        """The packed weights (pack_weights) as a new float32 tensor on the device: what an optimiser owns.  The padding floats have a
+        zero gradient, so they stay zero under Adam.  load_state_dict_nets(unpack_weights(w)) puts trained weights back."""
+        return torch.from_numpy(self._packed.copy()).to(self.device)
+
+    def _head_weight_gradient(self, features, grad_q, wdev, baseband_weight=None):
+        """(g [ML_WEIGHTS] float32, g_baseband_weight 0-dim float32) of sum_b grad_q[b] Q[b]: one cvvdp_ml_saliency_head_grad call per
+        band into one float64 accumulator."""
+        B, C, bands = self._check_features(features, baseband_weight)
+        gq = torch.ones((B,), dtype=torch.float32, device=self.device) if grad_q is None else \
+            torch.as_tensor(grad_q).detach().to(self.device, torch.float32).contiguous().reshape(-1)
+        if gq.numel() != B:
+            raise ValueError(f"grad_q has {gq.numel()} values for {B} batch items")
+        mask = sum(1 << s for s in set(self.disabled_features or ()))
+        lib = _capi.lib()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        no_bands = len(features)
+        with torch.cuda.device(self.device):
+            acc = torch.zeros((_capi.ML_WEIGHTS,), dtype=torch.float64, device=self.device)
+            d_scale = torch.zeros((B,), dtype=torch.float32, device=self.device)
+            for bb, (f, scale) in enumerate(bands):
+                if f.data_ptr() % (16 if C == 4 else 8):
+                    f = f.clone()
+                _, F, Hc, Wc = (int(n) for n in f.shape[:4])
+                nbytes = lib.cvvdp_ml_saliency_head_grad_scratch_bytes(B, F, Hc, Wc)
+                scratch = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
+                last = bb == no_bands - 1
+                rc = lib.cvvdp_ml_saliency_head_grad(self._handle, f.data_ptr(), B, F, Hc, Wc, C, wdev.data_ptr(), scale, mask, gq.data_ptr(),
+                                                     acc.data_ptr(), d_scale.data_ptr() if last else None, scratch.data_ptr(), nbytes, stream)
+                _capi.check(self._handle, rc, "cvvdp_ml_saliency_head_grad")
+            # Q[b] = ... + (baseband_weight / bands) (image_int) d_scale[b] on the last band
+            factor = (1.0 / no_bands) * (float(f32(self.parameters["image_int"])) if C == 3 else 1.0)
+            g_bw = ((gq.double() * d_scale.double()).sum() * factor).float()
+            return acc.float(), g_bw
+
+    def do_pooling_and_jods_with_weight_gradient(self, features, grad_q=None, weights=None):
+        """(Q [B], g [ML_WEIGHTS] float32, g_baseband_weight) on the device: Q_JOD of do_pooling_and_jods (the same kernel: the same
+        bits) and the gradient of sum_b grad_q[b] Q[b] (grad_q: ones) in the packed weights and in the model's scalar baseband_weight.
+        weights: a packed float32 tensor (weight_tensor()) in place of the metric's own networks.  torch's conventions (relu'(0) = 0);
+        entries that cannot act are exactly 0: the first-layer columns of an image's fourth channel and of disabled_features, the
+        padding.  The same bits on every call; features and weights are only read."""
+        wdev = self._weights_arg(weights)
+        Q = self._head_forward(features, wdev)
+        g, g_bw = self._head_weight_gradient(features, grad_q, wdev)
+        return Q, g, g_bw
+
+    def differentiable_jods(self, features, weights, baseband_weight=None):
+        """Q_JOD [B] attached to autograd in `weights` (a packed float32 tensor, weight_tensor()) and, if given, in the scalar tensor
+        `baseband_weight`, whose value then replaces the model's.  backward() runs the HIP gradient with the upstream factors as
+        grad_q.  The features carry no gradient."""
+        if not torch.is_tensor(weights):
+            raise ValueError("differentiable_jods: weights must be a tensor (weight_tensor())")
+        if baseband_weight is not None and (not torch.is_tensor(baseband_weight) or baseband_weight.numel() != 1):
+            raise ValueError("differentiable_jods: baseband_weight must be a tensor of one value")
+        for f in features:
+            if torch.is_tensor(f) and f.requires_grad:
+                raise vq_exception("differentiable_jods: the gradient in the features is out of scope")
+        return _HeadJods.apply(self, features, weights, baseband_weight)
+
+    def predict_video_source_with_weight_gradient(self, vid_source, grad_q=None):
+        vid_source, size, (Q, g, g_bw) = self._score_source(vid_source, lambda features: self.do_pooling_and_jods_with_weight_gradient(features, grad_q))
+        return Q.squeeze(), g, g_bw, self._source_stats(vid_source, size)
+
+    def predict_with_weight_gradient(self, test_cont, reference_cont, dim_order="BCFHW", frames_per_second=0, grad_q=None):
+        """(Q_JOD as predict() returns it, g [ML_WEIGHTS], g_baseband_weight, stats): the features of the content, then
+        do_pooling_and_jods_with_weight_gradient.  Refuses what predict() refuses."""
+        vs = video_source_array(test_cont, reference_cont, frames_per_second, dim_order=dim_order, display_photometry=self.display_photometry)
+        return self.predict_video_source_with_weight_gradient(vs, grad_q)
 
     def full_name(self):
         return "ColorVideoVDP-ML-Saliency"

@@ -423,6 +423,27 @@ int cvvdp_ml_saliency_head(cvvdp_handle* h, const float* dev_features, int32_t B
                            const float* dev_weights, float scale, uint32_t disabled_mask, float* dev_q, void* dev_scratch,
                            size_t scratch_bytes, void* stream);
 
+/* Weight gradient of the cvvdp-ml-saliency head for ONE band: what autograd through cvvdp_ml_saliency.do_pooling_and_jods gives the
+ * reference in training.  Features, C, dev_weights (only read, both), scale and disabled_mask are those of cvvdp_ml_saliency_head, which
+ * subtracts from Q[b] the mean over the item's cells of relu(feature_net) * relu(att_net) * scale.  For every packed weight and bias w
+ *   dev_acc[w] += sum over b of dev_gq[b] * dQ[b]/dw          dev_gq float [B]: dLoss/dQ[b]; dev_acc double [CVVDP_ML_WEIGHTS], 8-byte
+ * aligned, ADDED to (the caller zeroes it once and calls per band); the padding floats of the packing are not touched.  dev_d_scale
+ * (float [B], or NULL) receives dQ[b]/dscale of this band, -mean(relu(feature_net) * relu(att_net)): times scale / baseband_weight on
+ * the last band it is the gradient in the model's baseband_weight.  torch's conventions: relu'(0) = 0 on the hidden layers and on both
+ * outputs; the square roots and disabled_mask act on the inputs as in the forward, so the first-layer columns of an image's absent
+ * fourth channel and of disabled statistics come out as exactly 0.
+ *   dev_scratch   the scratch size function's bytes for (B, F, Hc, Wc), 4-byte aligned: the activations of the cells in flight, one
+ *                 row of CVVDP_ML_WEIGHTS partial sums per block, one float per (batch item, chunk of 256 cells)
+ * The forward inside runs in double (the relus decide as a float64 evaluation does); the deltas and the weight gradient are fp32.
+ * Sums over the 256 cells of a chunk, and over the chunks a block walks, run in cell order in fp32; the blocks' sums are added in block
+ * order in double.  No atomics, and the launch geometry depends on the shape alone: the same bits on every call.  Invalid arguments
+ * (as for cvvdp_ml_saliency_head; dev_acc not 8-byte aligned) give CVVDP_E_ARG before any launch.  Needs no configured clip and touches
+ * no handle state.  Added within ABI 14: new entries only. */
+size_t cvvdp_ml_saliency_head_grad_scratch_bytes(int32_t B, int32_t F, int32_t Hc, int32_t Wc);
+int cvvdp_ml_saliency_head_grad(cvvdp_handle* h, const float* dev_features, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C,
+                                const float* dev_weights, float scale, uint32_t disabled_mask, const float* dev_gq, double* dev_acc,
+                                float* dev_d_scale, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Head of the cvvdp-ml-transformer metric (cvvdp_ml_transformer.do_pooling_and_jods, pycvvdp/cvvdp_ml_metric.py:553-678) for ONE band of
  * the features cvvdp_get_features delivers (dev_features as for cvvdp_ml_saliency_head, but 4-byte alignment is enough: fp32
  * [B][F][Hc][Wc][C][6], C = 4 for a video, C = 3 for an image; only read).  Every (batch item, frame) is a sequence of N = Hc * Wc + 1
