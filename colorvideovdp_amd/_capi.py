@@ -190,6 +190,13 @@ SYMBOLS = {
     # (handle, features, B, F, Hc, Wc, C, weights, scale, mask, gq, acc, d_scale, scratch, bytes, stream)
     "cvvdp_ml_saliency_head_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # (handle, features, B, F, Hc, Wc, C, weights, scale, mask, gfeat, bytes, stream)
+    "cvvdp_ml_saliency_head_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float,
+                                                    C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cvvdp_ml_image_gradient_scratch_bytes": (C.c_size_t, [C.c_void_p]),
+    # (handle, test, strides, features[bands], gfeat[bands], bands, grad, strides, bytes, scratch, bytes, stream)
+    "cvvdp_ml_image_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
+                                          C.c_void_p, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cvvdp_ml_transformer_head_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "cvvdp_ml_transformer_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -186,8 +186,9 @@ void blur_pass(const float* in, float* out, int H, int W, int planes, bool verti
 }
 
 // levels finest first, the baseband, then the totals coarsest first: B items of NC channels (NC * B planes fit a grid's y: grad_host.cpp checks)
+// hk: the caller launches the point step of every level and the baseband itself (the ML metric's pooling adjoint, ml_image_grad.hip)
 template <int NC>
-void launch_chain(const GradChain<NC>& c, hipStream_t s) {
+void launch_chain(const GradChain<NC>& c, hipStream_t s, const GradChainHooks* hk = nullptr) {
   const int L = c.L, B = c.items;
   const bool test = c.wrt == 0 || (c.wrt & CVVDP_WRT_TEST), ref = c.wrt & CVVDP_WRT_REFERENCE;
   for (int l = 0; l + 1 < L; ++l) {
@@ -198,7 +199,8 @@ void launch_chain(const GradChain<NC>& c, hipStream_t s) {
       blur_pass(a.t0, a.t1, a.H, a.W, NC * B, true, false, a.taps, s);
       blur_pass(a.t1, a.t0, a.H, a.W, NC * B, false, false, a.taps, s);
     }
-    hipLaunchKernelGGL(k_grad_point<NC>, grid, dim3(GT), 0, s, a);
+    if (hk) hk->point(hk->ctx, l, s);
+    else hipLaunchKernelGGL(k_grad_point<NC>, grid, dim3(GT), 0, s, a);
     if (a.blur) {
       blur_pass(a.t1, a.t0, a.H, a.W, NC * B, false, true, a.taps, s);
       blur_pass(a.t0, a.t1, a.H, a.W, NC * B, true, true, a.taps, s);
@@ -211,7 +213,8 @@ void launch_chain(const GradChain<NC>& c, hipStream_t s) {
     }
   }
   if (test) {
-    hipLaunchKernelGGL(k_grad_base<NC>, dim3(B), dim3(256), 0, s, c.base);
+    if (hk) hk->base(hk->ctx, s);
+    else hipLaunchKernelGGL(k_grad_base<NC>, dim3(B), dim3(256), 0, s, c.base);
     for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_grad_accum<NC>, pixel_grid(c.acc[l].H, c.acc[l].W, B), dim3(GT), 0, s, c.acc[l]);
   }
   if (ref) {
@@ -233,6 +236,8 @@ void launch_image_gradient(const GradPlan& p, hipStream_t s) {
 }
 
 void launch_grad_chain4(const GradChain<4>& c, hipStream_t s) { launch_chain<4>(c, s); }
+void launch_grad_chain3_hooked(const GradChain<3>& c, const GradChainHooks& hk, hipStream_t s) { launch_chain<3>(c, s, &hk); }
+void launch_grad_display(const GradDisplayArgs& d, hipStream_t s) { hipLaunchKernelGGL(k_grad_display, pixel_grid(d.H, d.W, d.B), dim3(GT), 0, s, d); }
 
 // the parameter gradient (grad_param.hip) runs the first steps of a level's chain: the same kernels, launched as launch_chain does
 void launch_grad_min3(const GradBandArgsT<3>& a, hipStream_t s) { hipLaunchKernelGGL(k_grad_min<3>, pixel_grid(a.H, a.W, a.B), dim3(GT), 0, s, a); }

@@ -183,9 +183,11 @@ GRAD_HD void g_band_min(const GradBandArgsT<NC>& a, int item, int y, int x, floa
 // pass 3: from the (blurred) mask v = Mmm / 10^mask_c of the pixel, with gD = dJOD/dD:
 //   G[k]   = dJOD/dv[k]: the masking term gM = -gDu Du / (1 + M) through the transposed cross-channel weights and safe_pow'
 //   dir[c] = the part of dJOD/dT'[c] that comes straight through |T' - R'|
-template <int NC>
-GRAD_HD void g_band_point(const GradBandArgsT<NC>& a, int item, int y, int x, const float (&v)[NC], float (&G)[NC], float (&dir)[NC]) {
-  GradPixelT<NC> px;
+// (g_band_point_px: the same with gD = gD_of(c, D) in the caller's hands, and the pixel's forward values handed back: the pooling
+// adjoint of the ML metric, ml_image_grad_dev.h, takes dJOD/dD per pixel from its feature cell)
+template <int NC, class GD>
+GRAD_HD void g_band_point_px(const GradBandArgsT<NC>& a, int item, int y, int x, const float (&v)[NC], float (&G)[NC], float (&dir)[NC],
+                             GradPixelT<NC>& px, GD gD_of) {
   g_band_pixel(a, item, y, x, px);
   float C[NC], Mm[NC];
   for (int k = 0; k < NC; ++k) {
@@ -201,7 +203,7 @@ GRAD_HD void g_band_point(const GradBandArgsT<NC>& a, int item, int y, int x, co
     const float Du = (g_pow(d + kEps, a.mask_p) - a.eps_p) * inv1M;                   // :856
     const float sum = a.dmax + Du;
     const float D = a.dmax * Du / sum;                                                // soft clamp, :949-950
-    const float gD = a.coef[((int64_t)item * NC + c) * a.L + a.level] * (D + kEps);   // lp_norm, beta = 2: coef holds dJOD/dQ / (N (Q + sqrt(eps)))
+    const float gD = gD_of(c, D);
     const float gDu = gD * (a.dmax / sum) * (a.dmax / sum);
     dir[c] = gDu * inv1M * a.mask_p * g_pow(d + kEps, a.mask_p - 1.0f) * g_sign(diff);
     gM[c] = -gDu * Du * inv1M;
@@ -211,6 +213,12 @@ GRAD_HD void g_band_point(const GradBandArgsT<NC>& a, int item, int y, int x, co
     for (int c = 0; c < NC; ++c) gC += gM[c] * a.xw[k * NC + c];
     G[k] = gC * a.q[k] * g_pow(fabsf(Mm[k]) + kEps, a.q[k] - 1.0f) * g_sign(Mm[k]) * a.mask_c10;
   }
+}
+template <int NC>
+GRAD_HD void g_band_point(const GradBandArgsT<NC>& a, int item, int y, int x, const float (&v)[NC], float (&G)[NC], float (&dir)[NC]) {
+  GradPixelT<NC> px;
+  // lp_norm, beta = 2: coef holds dJOD/dQ / (N (Q + sqrt(eps)))
+  g_band_point_px(a, item, y, x, v, G, dir, px, [&a, item](int c, float D) { return a.coef[((int64_t)item * NC + c) * a.L + a.level] * (D + kEps); });
 }
 
 // pass 5: gm = dJOD/dm (the blur's adjoint of G), dir from pass 3 -> d[c] = dJOD/d(layer_c) (= the direct part of dJOD/dg_l) and

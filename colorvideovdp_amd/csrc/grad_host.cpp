@@ -12,8 +12,11 @@ using namespace cvvdp;
 // cvvdp_image_gradient (grad.hip), cvvdp_video_gradient (grad_video.hip), cvvdp_video_gradient_blocks_begin / cvvdp_video_gradient_block
 // (grad_blocks.hip) and cvvdp_param_gradient (grad_param.hip) share one scratch layout, one ordered refusal list and one band chain.
 namespace {
-enum GradRoute { kGradImage, kGradVideo, kGradBlocksBegin, kGradBlocksBlock, kGradParam };
-const char* const kGradName[] = {"image_gradient", "video_gradient", "video_gradient_blocks_begin", "video_gradient_block", "param_gradient"};
+enum GradRoute { kGradImage, kGradVideo, kGradBlocksBegin, kGradBlocksBlock, kGradParam, kGradMlImage };
+const char* const kGradName[] = {"image_gradient", "video_gradient", "video_gradient_blocks_begin", "video_gradient_block", "param_gradient",
+                                 "ml_image_gradient"};
+// cvvdp_ml_image_gradient (ml_image_grad.hip) is the image route with the features on: the image's layout, its own line in the refusal list
+bool image_route(GradRoute r) { return r == kGradImage || r == kGradMlImage; }
 // What a route keeps in the caller's scratch: the band chain's NC channels over `items` items with n_t temporaries and, per level, its
 // outputs or none; the extras in floats (0: none).  Call it for a configured handle only.
 // sides: how many sets of per-level outputs (and carries) the route keeps: 2 for CVVDP_WRT_BOTH, else 1 (the reference alone takes the test's place).
@@ -24,7 +27,7 @@ GradShape grad_shape(const cvvdp_handle* h, GradRoute r, int32_t wrt = CVVDP_WRT
   const size_t B = (size_t)c.batch, F = (size_t)c.n_frames, fl = (size_t)c.filter_len, block = (size_t)h->items_cap;
   const int sides = wrt == CVVDP_WRT_BOTH ? 2 : 1;
   switch (r) {
-    case kGradImage: return {3, B, 3, true, 0, 0, 0, false, sides};
+    case kGradImage: case kGradMlImage: return {3, B, 3, true, 0, 0, 0, false, sides};
     case kGradVideo: return {4, F * B, 3, true, 0, 4 * F * F, 0, false, sides};            // wt: the gather variant's table [4][F][F]
     case kGradParam: return {h->nch, block, 2, false, 0, 0, 0, true, 1};                   // a full block (an image: 1 * batch)
     default:         return {4, block, 3, true, 2 * B, 4 * (fl - 1) * fl, fl * 3 * B * (size_t)h->lv[0].P, false, sides};
@@ -86,14 +89,20 @@ int grad_checks(const cvvdp_handle* h, cvvdp_handle* say, GradRoute r, bool null
                                            : "%s: tensors and gradients must be 4-byte aligned, the scratch 16-byte aligned");
   if (!h->configured) return no(CVVDP_E_STATE, "%s: configure first");
   const cvvdp_clip& c = h->c;
-  if (r == kGradImage && c.is_video) return no(CVVDP_E_STATE, "%s: configured for video; the gradient exists for images only");
-  if (r != kGradImage && r != kGradParam && !c.is_video) return no(CVVDP_E_STATE, "%s: configured for an image (cvvdp_image_gradient)");
+  if (image_route(r) && c.is_video) return no(CVVDP_E_STATE, "%s: configured for video; the gradient exists for images only");
+  if (!image_route(r) && r != kGradParam && !c.is_video) return no(CVVDP_E_STATE, "%s: configured for an image (cvvdp_image_gradient)");
   if (c.channels != 3) return no(CVVDP_E_UNSUPPORTED, "%s: 1-channel content is out of scope");
   if (r == kGradImage && !say) return CVVDP_OK;
-  if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) return no(CVVDP_E_UNSUPPORTED, "%s: not with a heat map or features");
+  if (r == kGradMlImage) {
+    if (wrt != CVVDP_WRT_TEST) return no(CVVDP_E_UNSUPPORTED, "%s: the gradient in the reference is out of scope (the sensitivity and the R statistics move with it)");
+    if (c.heatmap != CVVDP_HEATMAP_NONE) return no(CVVDP_E_UNSUPPORTED, "%s: not with a heat map");
+    if (c.feature_size <= 0) return no(CVVDP_E_STATE, "%s: the image must be scored with features (cvvdp_clip.feature_size > 0)");
+  } else if (c.heatmap != CVVDP_HEATMAP_NONE || c.feature_size > 0) {
+    return no(CVVDP_E_UNSUPPORTED, "%s: not with a heat map or features");
+  }
   if (say && r != kGradParam && (h->p.eotf == CVVDP_EOTF_PQ || h->p.eotf == CVVDP_EOTF_HLG))
     return no(CVVDP_E_UNSUPPORTED, "%s: PQ and HLG displays are refused (the reference's own gradient is NaN at a sample of 0)");
-  if (r != kGradImage) {
+  if (!image_route(r)) {
     if (c.defer_bands) return no(CVVDP_E_STATE, "%s: not for clips scored in pieces (defer_bands)");
     if (r == kGradVideo && c.block_frames < c.n_frames)
       return no(CVVDP_E_STATE, "%s: the clip must be one temporal block (block_frames %d < n_frames %d)", c.block_frames, c.n_frames);
@@ -102,7 +111,7 @@ int grad_checks(const cvvdp_handle* h, cvvdp_handle* say, GradRoute r, bool null
   }
   const GradShape s = grad_shape(h, r, wrt);
   if (s.items * (size_t)s.NC > 65535) {      // (NC planes per item in a grid's y)
-    if (r == kGradImage) return no(CVVDP_E_UNSUPPORTED, "%s: batch of %d too large", c.batch);
+    if (image_route(r)) return no(CVVDP_E_UNSUPPORTED, "%s: batch of %d too large", c.batch);
     return no(CVVDP_E_UNSUPPORTED, "%s: %s%d frames x %d batch items are too many (%d planes per item, 65535 at most)",
               r == kGradVideo || r == kGradParam ? "" : "blocks of ", r == kGradVideo ? c.n_frames : (c.is_video ? c.block_frames : 1), c.batch, s.NC);
   }
@@ -125,10 +134,10 @@ int grad_front(cvvdp_handle* h, GradRoute r, bool null_arg, bool misaligned, con
     int64_t last = 0, term = 0;
     bool bad = false;
     for (int k = 0; k < 5 && !bad; ++k) {
-      if (k == 2 && r == kGradImage) continue;
+      if (k == 2 && image_route(r)) continue;
       bad = sg[k] < 0 || st[k] < 0 || __builtin_mul_overflow(dims[k] - 1, sg[k], &term) || __builtin_add_overflow(last, term, &last);
     }
-    if ((bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float))) && r == kGradImage)
+    if ((bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float))) && image_route(r))
       return host_fail(h, CVVDP_E_ARG, "%s: the gradient buffer of %zu bytes does not hold %d x 3 x %d x %d samples at these strides", what, grad_bytes, c.batch,
                   c.height, c.width);
     if (bad || (uint64_t)last >= (uint64_t)(grad_bytes / sizeof(float)))
@@ -281,6 +290,37 @@ int cvvdp::grad_prepare(cvvdp_handle* h, const GradSides& sd, void* scratch, siz
   };
   if (sd.wrt & CVVDP_WRT_TEST) display(plan.dsp, sc + lay.d[0], sd.test, sd.st, sd.grad, sd.sg);
   if (sd.wrt & CVVDP_WRT_REFERENCE) display(plan.dsp_r, sc + lay.d_r[0], sd.ref, sd.sr, sd.grad_r, sd.sgr);
+  return CVVDP_OK;
+}
+// The ML metric's image gradient: the image plan without the pooling of Q_per_ch; per band the caller's features and their gradients.
+size_t cvvdp::ml_image_grad_scratch(const cvvdp_handle* h) { return grad_scratch_bytes(h, kGradMlImage); }
+int cvvdp::ml_image_grad_prepare(cvvdp_handle* h, const GradSides& sd, const float* const* feat, const float* const* gfeat, int32_t n_bands, void* scratch,
+                                 size_t scratch_bytes, MlImageGradPlan& plan) {
+  GradLayout lay;
+  if (h && (!feat || !gfeat)) return host_fail(h, CVVDP_E_ARG, "ml_image_gradient: null argument");
+  if (int rc = grad_front_sides(h, kGradMlImage, sd, scratch, scratch_bytes, lay)) return rc;
+  if (!h->ws || !h->image_scored) return host_fail(h, CVVDP_E_STATE, "ml_image_gradient: valid after cvvdp_put_image and cvvdp_process_image");
+  const int B = h->c.batch, L = h->L, fs = h->c.feature_size;
+  if (n_bands != L) return host_fail(h, CVVDP_E_ARG, "ml_image_gradient: features of %d bands, the image has %d", n_bands, L);
+  for (int l = 0; l < L; ++l) {
+    if (!feat[l] || !gfeat[l]) return host_fail(h, CVVDP_E_ARG, "ml_image_gradient: null features or feature gradients of band %d", l);
+    if (misaligned4(feat[l], gfeat[l])) return host_fail(h, CVVDP_E_ARG, "ml_image_gradient: the features and their gradients must be 4-byte aligned");
+  }
+  float* sc = static_cast<float*>(scratch);
+  plan = MlImageGradPlan{};
+  fill_grad_chain(h, B, sc, lay, sc + lay.coef, plan.chain, CVVDP_WRT_TEST);
+  for (int l = 0; l < L; ++l) {
+    MlGradCells& m = plan.cells[l];
+    m.feat = feat[l]; m.gfeat = gfeat[l]; m.fs = fs;
+    m.Hc = (h->lv[l].H + fs - 1) / fs; m.Wc = (h->lv[l].W + fs - 1) / fs;
+    for (int k = 0; k < 3; ++k) m.inv_gain[k] = l == L - 1 ? 1.0f : 1.0f / h->p.ch_gain[k];      // (cvvdp_get_features' own)
+  }
+  GradDisplayArgs& d = plan.dsp;
+  d.tot = sc + lay.d[0];
+  d.test = static_cast<const float*>(sd.test); d.tb = sd.st[0]; d.tc = sd.st[1]; d.th = sd.st[3]; d.tw = sd.st[4];
+  d.grad = sd.grad; d.gb = sd.sg[0]; d.gc = sd.sg[1]; d.gh = sd.sg[3]; d.gw = sd.sg[4];
+  d.H = h->c.height; d.W = h->c.width; d.B = B;
+  host_display(h, d.dm);
   return CVVDP_OK;
 }
 // One temporal block: items = n_frames * batch; level 0's d ends up as G, what the FIR adjoint reads.

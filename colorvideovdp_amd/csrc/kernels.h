@@ -702,6 +702,32 @@ size_t grad_wrt_scratch(const cvvdp_handle* h, int route, int32_t wrt);
 int grad_prepare(cvvdp_handle* h, const GradSides& sd, void* scratch, size_t scratch_bytes, GradPlan& plan);
 void launch_image_gradient(const GradPlan& p, hipStream_t s);
 
+// ---------------------------------------------------------------- the ML metric as an image loss (ml_image_grad.hip, ml_image_grad_dev.h)
+// d Q_JOD[b] / d test[b] of cvvdp-ml-saliency for the image scored last WITH features: the band chain above, where per pixel dQ/dD and
+// dQ/d|T'| come from the pixel's feature cell (the adjoint of the feature pooling) in place of the pooling of Q_per_ch.
+struct MlGradCells {         // the features of ONE band and their gradients from the head, as the pooling adjoint reads them
+  const float* feat;        // [B][Hc][Wc][3][6]
+  const float* gfeat;       // [B][Hc][Wc][3][6]: dQ[b] / d feat
+  int32_t fs, Hc, Wc;       // cell size (cvvdp_clip.feature_size) and the cells per column / row of the band
+  float inv_gain[3];        // 1 / ch_gain (the kernels' T' carries the channel gain, the features do not); 1 for the baseband
+};
+// launch_chain with the two steps that know where dJOD/dD comes from in the caller's hands (grad.hip)
+struct GradChainHooks {
+  const void* ctx;
+  void (*point)(const void* ctx, int level, hipStream_t s);      // in place of k_grad_point of a level
+  void (*base)(const void* ctx, hipStream_t s);                   // in place of k_grad_base
+};
+void launch_grad_chain3_hooked(const GradChain<3>& c, const GradChainHooks& hk, hipStream_t s);
+void launch_grad_display(const GradDisplayArgs& d, hipStream_t s);
+struct MlImageGradPlan {     // everything cvvdp_ml_image_gradient launches, filled by grad_host.cpp
+  GradChain<3> chain;       // (coef stays unread: no kernel of this plan looks at Q_per_ch)
+  MlGradCells cells[CVVDP_MAX_LEVELS];
+  GradDisplayArgs dsp;
+};
+size_t ml_image_grad_scratch(const cvvdp_handle* h);
+int ml_image_grad_prepare(cvvdp_handle* h, const GradSides& sd, const float* const* feat, const float* const* gfeat, int32_t n_bands, void* scratch,
+                          size_t scratch_bytes, MlImageGradPlan& plan);
+
 // ---------------------------------------------------------------- gradient of the video JOD (grad_video.hip, grad_video_dev.h)
 // d JOD[b] / d test[b] of a clip scored as ONE temporal block on the unfused route: the band chain above with four channels over
 // items = frames x batch (item = frame * B + b, the forward's order), then the adjoint of the temporal FIR fused with the display model's.

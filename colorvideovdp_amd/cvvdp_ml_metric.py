@@ -22,8 +22,14 @@ pass per band (cvvdp_ml_saliency_head_grad; csrc/ml_head_grad.hip)
 differentiable_jods (autograd), predict_with_weight_gradient; `calibration fit -m cvvdp-ml-saliency` runs Adam on them and writes a
 cvvdp.ckpt.  No dropout: the reference's MLPs carry Dropout(0.2) in training mode, the fit here is deterministic.
 
+cvvdp_ml_saliency as an image loss: predict_with_gradient / differentiable_loss give d Q_JOD / d test of an image.  The
+gradient of Q_JOD in the features, what the reference's autograd leaves in features[band].grad, is a third HIP pass per band
+(cvvdp_ml_saliency_head_input_grad; csrc/ml_head_input_grad.hip: do_pooling_and_jods_with_feature_gradient); the adjoint of the feature
+pooling takes it into the band chain of cvvdp's image gradient (cvvdp_ml_image_gradient; csrc/ml_image_grad.hip).  Clips and the
+gradient in the reference are refused; so is everything for the transformer head.
+
 Not available: heat maps, distograms, frame sharding, `RegressionTransformer.get_heatmap`, training of the transformer head, the
-gradient in the features or pixels.
+pixel gradient of clips and of the transformer metric.
 """
 import ctypes
 import logging
@@ -35,7 +41,7 @@ import torch
 from . import _capi
 from . import host_setup as hs
 from .config import config_files, json2dict
-from .cvvdp_metric import cvvdp
+from .cvvdp_metric import _JodLoss, cvvdp, reshuffle_dims
 from .video_source import video_source, video_source_array
 from .vq_metric import register_metric, vq_exception
 
@@ -293,6 +299,15 @@ class _cvvdp_ml(cvvdp):
                 yield f, scale
         return B, C, bands()
 
+    def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None, wrt="test"):
+        """Refused: cvvdp's pixel gradient differentiates the pooling of Q_per_ch, which these metrics replace by a trained head."""
+        raise vq_exception(f"{self._TITLE}: no pixel gradient for this head yet (predict_with_gradient and differentiable_loss are those of "
+                           "the cvvdp metric and of cvvdp_ml_saliency)")
+
+    def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None, wrt="test"):
+        """Refused, as predict_with_gradient."""
+        return self.predict_with_gradient(test, reference, dim_order, frames_per_second, block_frames, wrt)
+
     def short_name(self):
         return self.__class__.__name__.replace("_", "-")
 
@@ -399,6 +414,83 @@ class cvvdp_ml_saliency(_cvvdp_ml):
             factor = (1.0 / no_bands) * (float(f32(self.parameters["image_int"])) if C == 3 else 1.0)
             g_bw = ((gq.double() * d_scale.double()).sum() * factor).float()
             return acc.float(), g_bw
+
+    # ------------------------------------------------------------------ the gradient in the features
+    def _head_input_gradient(self, features, wdev, baseband_weight=None):
+        """[dQ[b] / d features[band][b]] as new float32 device tensors with the shapes of the features: one
+        cvvdp_ml_saliency_head_input_grad call per band."""
+        B, C, bands = self._check_features(features, baseband_weight)
+        mask = sum(1 << s for s in set(self.disabled_features or ()))
+        lib = _capi.lib()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        out = []
+        with torch.cuda.device(self.device):
+            for f, scale in bands:
+                if f.data_ptr() % (16 if C == 4 else 8):
+                    f = f.clone()
+                _, F, Hc, Wc = (int(n) for n in f.shape[:4])
+                g = torch.empty_like(f)
+                rc = lib.cvvdp_ml_saliency_head_input_grad(self._handle, f.data_ptr(), B, F, Hc, Wc, C, wdev.data_ptr(), scale, mask,
+                                                           g.data_ptr(), g.numel() * 4, stream)
+                _capi.check(self._handle, rc, "cvvdp_ml_saliency_head_input_grad")
+                out.append(g)
+        return out
+
+    def do_pooling_and_jods_with_feature_gradient(self, features, weights=None):
+        """(Q [B], [g per band]) on the device: Q_JOD of do_pooling_and_jods (the same kernel: the same bits) and per band
+        g[b, ...] = dQ[b] / d features[band][b, ...], float32 with the shape of the band's features: what autograd through the
+        reference's head leaves in features[band].grad for the loss Q.sum() (all six statistics, those of the reference included).
+        weights: a packed float32 tensor (weight_tensor()) in place of the metric's own networks.  torch's conventions (relu'(0) = 0);
+        where a variance is exactly 0 the derivative of sqrt(|v|) is taken as 0 (autograd gives NaN there); disabled_features have
+        gradient exactly 0.  The same bits on every call; features and weights are only read."""
+        wdev = self._weights_arg(weights)
+        return self._head_forward(features, wdev), self._head_input_gradient(features, wdev)
+
+    # ------------------------------------------------------------------ the metric as an image loss
+    def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None, wrt="test"):
+        """(jod, grad) of an image: `jod` as predict() returns it (the same kernels on the same tensors: the same bits), `grad` =
+        d jod / d test, float32 on the device, with the shape of `test` in the caller's dim_order; for a batch, grad[b] is the gradient
+        of jod[b] (items do not interact; the reference may have a batch of 1).  float32 tensors on the metric's device, three channels,
+        one frame; sRGB, numeric-gamma and linear displays.  Refused with a vq_exception: clips, wrt = "reference" / "both" (the
+        sensitivity and the R statistics move with the reference), and what cvvdp.predict_with_gradient refuses (1-channel content,
+        other dtypes, PQ / HLG displays).  The backward: the head's gradient in the features (cvvdp_ml_saliency_head_input_grad),
+        then cvvdp_ml_image_gradient on the pyramid the forward left in the workspace.  The same bits on every run."""
+        if wrt != "test" and isinstance(wrt, str) and wrt in _capi.WRT:      # (anything else: _gradient_inputs names the valid values)
+            raise vq_exception(f'{self._TITLE}: predict_with_gradient has no gradient in the reference (wrt = {wrt!r}): the sensitivity and the '
+                               'R statistics of the features move with it; wrt = "test" only')
+        order = str(dim_order).upper()
+        if torch.is_tensor(test) and len(order) == test.dim() and "F" in order and test.shape[order.index("F")] > 1:
+            raise vq_exception(f"{self._TITLE}: predict_with_gradient is for images, clips are out of scope "
+                               f"({test.shape[order.index('F')]} frames were passed)")
+        t, r = self._gradient_inputs(test, reference, dim_order, 0, None, wrt)
+        if self._shard is not None:
+            raise vq_exception("predict_with_gradient: not available with frame sharding")
+        vs = video_source_array(t, r, 0, dim_order="BCFHW", display_photometry=self.display_photometry)
+        features, _ = self.extract_features(vs)
+        wdev = self._weights_arg(None)
+        jod = self._head_forward(features, wdev)
+        gfeat = self._head_input_gradient(features, wdev)
+        lib = _capi.lib()
+        grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
+        gv = reshuffle_dims(grad, dim_order, "BCFHW")                # a view: the kernel writes the caller's layout through its strides
+        assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
+        n = len(features)
+        pf, pg = (ctypes.c_void_p * n)(*(f.data_ptr() for f in features)), (ctypes.c_void_p * n)(*(g.data_ptr() for g in gfeat))
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(max(int(lib.cvvdp_ml_image_gradient_scratch_bytes(self._handle)), 16), dtype=torch.uint8, device=self.device)
+            rc = lib.cvvdp_ml_image_gradient(self._handle, t.data_ptr(), (ctypes.c_int64 * 5)(*t.stride()), pf, pg, n, gv.data_ptr(),
+                                             (ctypes.c_int64 * 5)(*gv.stride()), grad.numel() * 4, scratch.data_ptr(), scratch.numel(),
+                                             ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(self._handle, rc, "cvvdp_ml_image_gradient")
+        return jod.squeeze(), grad
+
+    def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None, wrt="test"):
+        """10 - JOD of an image as a tensor attached to autograd (cvvdp.differentiable_loss: the same autograd function).  backward()
+        multiplies the gradient predict_with_gradient() stored by the upstream gradient, one factor per batch item; the reference
+        receives None, and a reference that requires a gradient is refused."""
+        if torch.is_tensor(reference) and reference.requires_grad:
+            raise vq_exception(f"{self._TITLE}: differentiable_loss has no gradient for the reference")
+        return _JodLoss.apply(test, reference, self, dim_order, frames_per_second, block_frames, wrt)
 
     def do_pooling_and_jods_with_weight_gradient(self, features, grad_q=None, weights=None):
         """(Q [B], g [ML_WEIGHTS] float32, g_baseband_weight) on the device: Q_JOD of do_pooling_and_jods (the same kernel: the same

@@ -444,6 +444,45 @@ int cvvdp_ml_saliency_head_grad(cvvdp_handle* h, const float* dev_features, int3
                                 const float* dev_weights, float scale, uint32_t disabled_mask, const float* dev_gq, double* dev_acc,
                                 float* dev_d_scale, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* Gradient of the cvvdp-ml-saliency head IN ITS INPUTS for ONE band: what autograd through cvvdp_ml_saliency.do_pooling_and_jods leaves
+ * the reference in features[band].grad.  Features, C, dev_weights (only read, both), scale and disabled_mask are those of
+ * cvvdp_ml_saliency_head.  For every statistic of every cell
+ *   dev_gfeat[b][f][y][x][c][s] = dQ[b] / d dev_features[b][f][y][x][c][s]      fp32 [B][F][Hc][Wc][C][6], aligned as dev_features
+ * (all six statistics, those of the reference R included; for a loss sum_b gq[b] Q[b] the caller scales item b by gq[b]).  The chain:
+ * Q[b] -= mean over the item's cells of relu(feature_net) * relu(att_net) * scale; torch's relu'(0) = 0 on the hidden layers and on both
+ * outputs; a variance v entered the nets as sqrt(|v|), whose derivative sign(v) / (2 sqrt(|v|)) is taken as 0 at v == 0 (autograd
+ * gives NaN there); a statistic named in disabled_mask has gradient exactly 0; an image's absent fourth channel is not part of the
+ * output.  gfeat_bytes: the size of dev_gfeat, at least that of the features; the two must not overlap.
+ * One thread per cell; the forward inside runs in double and only its relu decisions are kept, the deltas are summed in double and
+ * rounded to fp32 between layers.  No sums over cells, no atomics, no scratch, geometry from the shape alone: the same bits on every
+ * call.  Invalid arguments (as for cvvdp_ml_saliency_head; a short or overlapping dev_gfeat) give CVVDP_E_ARG before any launch.
+ * Needs no configured clip and touches no handle state.  Added within ABI 14: new entries only. */
+int cvvdp_ml_saliency_head_input_grad(cvvdp_handle* h, const float* dev_features, int32_t B, int32_t F, int32_t Hc, int32_t Wc, int32_t C,
+                                      const float* dev_weights, float scale, uint32_t disabled_mask, float* dev_gfeat, size_t gfeat_bytes,
+                                      void* stream);
+
+/* The cvvdp-ml-saliency metric as an image loss: d Q_JOD[b] / d test[b] of the image scored last WITH features (cvvdp_clip.feature_size
+ * > 0; cvvdp_put_image, cvvdp_process_image), through the adjoint of the feature pooling and the backward of cvvdp_image_gradient.
+ *   dev_features, dev_gfeat   host arrays of n_bands device pointers: per band the features cvvdp_get_features delivered, fp32
+ *                             [B][Hc][Wc][3][6], and dQ[b] / d features from cvvdp_ml_saliency_head_input_grad, the same shape; 4-byte
+ *                             aligned, only read.  n_bands is the image's number of bands.  The buffers carry no byte counts: band l
+ *                             (level 0 is height x width, H_l = (H_{l-1} + 1) / 2, W_l likewise) must hold exactly
+ *                             batch * ceil(H_l / feature_size) * ceil(W_l / feature_size) * 18 floats, and the kernels index up to
+ *                             the last of them, what cvvdp_get_features wrote for that band
+ *   dev_test, dev_grad        as for cvvdp_image_gradient: the float32 test tensor the image was put from and the gradient, both through
+ *                             strides in elements (B, C, F, H, W; F is not looked at)
+ *   dev_scratch               cvvdp_ml_image_gradient_scratch_bytes(h) bytes, 16-byte aligned (the layout of cvvdp_image_gradient)
+ * Per pixel p of cell k (n_k pixels; the last cells of a row / column are ragged) and channel c, for X in {|T_f| S, D}:
+ * dQ/dX_p = (g_mean[k, c] + 2 g_var[k, c] (X_p - mean[k, c])) / n_k, the mean being the feature itself.  The reference's statistics and
+ * the sensitivity are constants here: the gradient in the reference is not available.  Gathers, no atomics: the same bits on every
+ * call.  Refused before any launch: null / misaligned pointers, a short scratch or gradient buffer, another number of bands
+ * (CVVDP_E_ARG); no image scored, a clip, features off (CVVDP_E_STATE); 1-channel content, a heat map, PQ / HLG displays
+ * (CVVDP_E_UNSUPPORTED).  The entries of cvvdp_image_gradient keep refusing a clip configured with features.  Added within ABI 14. */
+size_t cvvdp_ml_image_gradient_scratch_bytes(const cvvdp_handle* h);
+int cvvdp_ml_image_gradient(cvvdp_handle* h, const void* dev_test, const int64_t strides_test[5], const float* const* dev_features,
+                            const float* const* dev_gfeat, int32_t n_bands, float* dev_grad, const int64_t strides_grad[5], size_t grad_bytes,
+                            void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Head of the cvvdp-ml-transformer metric (cvvdp_ml_transformer.do_pooling_and_jods, pycvvdp/cvvdp_ml_metric.py:553-678) for ONE band of
  * the features cvvdp_get_features delivers (dev_features as for cvvdp_ml_saliency_head, but 4-byte alignment is enough: fp32
  * [B][F][Hc][Wc][C][6], C = 4 for a video, C = 3 for an image; only read).  Every (batch item, frame) is a sequence of N = Hc * Wc + 1
