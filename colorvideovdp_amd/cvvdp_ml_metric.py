@@ -41,7 +41,8 @@ import torch
 from . import _capi
 from . import host_setup as hs
 from .config import config_files, json2dict
-from .cvvdp_metric import _JodLoss, cvvdp, reshuffle_dims
+from ._pixel_grad import GradOut, PixelLoss
+from .cvvdp_metric import cvvdp
 from .video_source import video_source, video_source_array
 from .vq_metric import register_metric, vq_exception
 
@@ -361,17 +362,26 @@ class cvvdp_ml_saliency(_cvvdp_ml):
         w = weights.detach().to(self.device).contiguous().reshape(-1)
         return w.clone() if w.data_ptr() % 16 else w
 
-    def _head_forward(self, features, wdev, baseband_weight=None):
+    def _head_bands(self, features, baseband_weight=None):
+        """What the head's three passes share: B, C, the mask of disabled_features, the library, the current stream and an iterator over
+        the bands of _check_features as (features, F, H', W', scale), the features cloned if they are not aligned to what the kernels
+        read at a time (16 bytes for four channels, 8 for three: a view into a larger buffer may not be)."""
         B, C, bands = self._check_features(features, baseband_weight)
+
+        def aligned():
+            for f, scale in bands:
+                if f.data_ptr() % (16 if C == 4 else 8):
+                    f = f.clone()
+                yield (f,) + tuple(int(n) for n in f.shape[1:4]) + (scale,)
+
         mask = sum(1 << s for s in set(self.disabled_features or ()))
-        lib = _capi.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return B, C, mask, _capi.lib(), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), aligned()
+
+    def _head_forward(self, features, wdev, baseband_weight=None):
+        B, C, mask, lib, stream, bands = self._head_bands(features, baseband_weight)
         with torch.cuda.device(self.device):
             Q = torch.full((B,), 10.0, dtype=torch.float32, device=self.device)
-            for f, scale in bands:
-                if f.data_ptr() % (16 if C == 4 else 8):           # (a view into a larger buffer: the kernel reads 16 / 8 bytes at a time)
-                    f = f.clone()
-                _, F, Hc, Wc = (int(n) for n in f.shape[:4])
+            for f, F, Hc, Wc, scale in bands:
                 nbytes = lib.cvvdp_ml_saliency_head_scratch_bytes(B, F, Hc, Wc)
                 scratch = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
                 rc = lib.cvvdp_ml_saliency_head(self._handle, f.data_ptr(), B, F, Hc, Wc, C, wdev.data_ptr(), scale, mask,
@@ -388,22 +398,16 @@ class cvvdp_ml_saliency(_cvvdp_ml):
     def _head_weight_gradient(self, features, grad_q, wdev, baseband_weight=None):
         """(g [ML_WEIGHTS] float32, g_baseband_weight 0-dim float32) of sum_b grad_q[b] Q[b]: one cvvdp_ml_saliency_head_grad call per
         band into one float64 accumulator."""
-        B, C, bands = self._check_features(features, baseband_weight)
+        B, C, mask, lib, stream, bands = self._head_bands(features, baseband_weight)
         gq = torch.ones((B,), dtype=torch.float32, device=self.device) if grad_q is None else \
             torch.as_tensor(grad_q).detach().to(self.device, torch.float32).contiguous().reshape(-1)
         if gq.numel() != B:
             raise ValueError(f"grad_q has {gq.numel()} values for {B} batch items")
-        mask = sum(1 << s for s in set(self.disabled_features or ()))
-        lib = _capi.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         no_bands = len(features)
         with torch.cuda.device(self.device):
             acc = torch.zeros((_capi.ML_WEIGHTS,), dtype=torch.float64, device=self.device)
             d_scale = torch.zeros((B,), dtype=torch.float32, device=self.device)
-            for bb, (f, scale) in enumerate(bands):
-                if f.data_ptr() % (16 if C == 4 else 8):
-                    f = f.clone()
-                _, F, Hc, Wc = (int(n) for n in f.shape[:4])
+            for bb, (f, F, Hc, Wc, scale) in enumerate(bands):
                 nbytes = lib.cvvdp_ml_saliency_head_grad_scratch_bytes(B, F, Hc, Wc)
                 scratch = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
                 last = bb == no_bands - 1
@@ -419,16 +423,10 @@ class cvvdp_ml_saliency(_cvvdp_ml):
     def _head_input_gradient(self, features, wdev, baseband_weight=None):
         """[dQ[b] / d features[band][b]] as new float32 device tensors with the shapes of the features: one
         cvvdp_ml_saliency_head_input_grad call per band."""
-        B, C, bands = self._check_features(features, baseband_weight)
-        mask = sum(1 << s for s in set(self.disabled_features or ()))
-        lib = _capi.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        B, C, mask, lib, stream, bands = self._head_bands(features, baseband_weight)
         out = []
         with torch.cuda.device(self.device):
-            for f, scale in bands:
-                if f.data_ptr() % (16 if C == 4 else 8):
-                    f = f.clone()
-                _, F, Hc, Wc = (int(n) for n in f.shape[:4])
+            for f, F, Hc, Wc, scale in bands:
                 g = torch.empty_like(f)
                 rc = lib.cvvdp_ml_saliency_head_input_grad(self._handle, f.data_ptr(), B, F, Hc, Wc, C, wdev.data_ptr(), scale, mask,
                                                            g.data_ptr(), g.numel() * 4, stream)
@@ -471,18 +469,15 @@ class cvvdp_ml_saliency(_cvvdp_ml):
         jod = self._head_forward(features, wdev)
         gfeat = self._head_input_gradient(features, wdev)
         lib = _capi.lib()
-        grad = torch.empty(test.shape, dtype=torch.float32, device=self.device)
-        gv = reshuffle_dims(grad, dim_order, "BCFHW")                # a view: the kernel writes the caller's layout through its strides
-        assert gv.untyped_storage().data_ptr() == grad.untyped_storage().data_ptr()
+        out = GradOut(test, reference, dim_order, wrt, self.device)
         n = len(features)
         pf, pg = (ctypes.c_void_p * n)(*(f.data_ptr() for f in features)), (ctypes.c_void_p * n)(*(g.data_ptr() for g in gfeat))
         with torch.cuda.device(self.device):
             scratch = torch.empty(max(int(lib.cvvdp_ml_image_gradient_scratch_bytes(self._handle)), 16), dtype=torch.uint8, device=self.device)
-            rc = lib.cvvdp_ml_image_gradient(self._handle, t.data_ptr(), (ctypes.c_int64 * 5)(*t.stride()), pf, pg, n, gv.data_ptr(),
-                                             (ctypes.c_int64 * 5)(*gv.stride()), grad.numel() * 4, scratch.data_ptr(), scratch.numel(),
-                                             ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            rc = lib.cvvdp_ml_image_gradient(self._handle, t.data_ptr(), (ctypes.c_int64 * 5)(*t.stride()), pf, pg, n, *out.args("test"),
+                                             scratch.data_ptr(), scratch.numel(), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         _capi.check(self._handle, rc, "cvvdp_ml_image_gradient")
-        return jod.squeeze(), grad
+        return jod.squeeze(), out.result()
 
     def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, block_frames=None, wrt="test"):
         """10 - JOD of an image as a tensor attached to autograd (cvvdp.differentiable_loss: the same autograd function).  backward()
@@ -490,7 +485,8 @@ class cvvdp_ml_saliency(_cvvdp_ml):
         receives None, and a reference that requires a gradient is refused."""
         if torch.is_tensor(reference) and reference.requires_grad:
             raise vq_exception(f"{self._TITLE}: differentiable_loss has no gradient for the reference")
-        return _JodLoss.apply(test, reference, self, dim_order, frames_per_second, block_frames, wrt)
+        predict = lambda: self.predict_with_gradient(test, reference, dim_order, frames_per_second, block_frames, wrt)
+        return PixelLoss.apply(test, reference, predict, 10.0, dim_order, wrt)
 
     def do_pooling_and_jods_with_weight_gradient(self, features, grad_q=None, weights=None):
         """(Q [B], g [ML_WEIGHTS] float32, g_baseband_weight) on the device: Q_JOD of do_pooling_and_jods (the same kernel: the same

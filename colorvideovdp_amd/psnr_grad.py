@@ -18,32 +18,9 @@ import ctypes
 import torch
 
 from . import _capi
-from .video_source import reshuffle_dims, video_source_array
+from ._pixel_grad import GradOut, PixelLoss, bcfhw_views, check_float32_tensors, check_same_clip, check_wrt
+from .video_source import video_source_array
 from .vq_metric import vq_exception
-
-
-class _PsnrLoss(torch.autograd.Function):
-    """-psnr [B] with the gradient of predict_with_gradient (differentiable_loss)."""
-
-    @staticmethod
-    def forward(ctx, test, reference, metric, dim_order, frames_per_second, wrt):
-        out = metric.predict_with_gradient(test, reference, dim_order, frames_per_second, wrt=wrt)
-        ctx.save_for_backward(*out[1:])
-        ctx.wrt, ctx.batch_dim = wrt, dim_order.upper().find("B")
-        return -out[0]
-
-    @staticmethod
-    def backward(ctx, upstream):
-        def scaled(g):
-            if ctx.batch_dim < 0:                 # no batch dimension: one item
-                return -g * upstream.reshape(())
-            shape = [1] * g.dim()
-            shape[ctx.batch_dim] = -1
-            return -g * upstream.reshape(shape)
-
-        out = [scaled(g) for g in ctx.saved_tensors]
-        g_test, g_ref = {"test": (out[0], None), "reference": (None, out[0])}.get(ctx.wrt) or out
-        return g_test, g_ref, None, None, None, None
 
 
 class psnr_gradient:
@@ -52,33 +29,17 @@ class psnr_gradient:
     _psnr_loss = False
 
     def _psnr_gradient_inputs(self, test, reference, dim_order, frames_per_second, wrt):
-        """What predict_with_gradient refuses, checked before anything touches the device; returns the BCFHW views.  The checks of
-        ssim_grad.ssim_gradient._gradient_inputs in its order, except that a tensor on another device is refused before the device
-        itself is asked for, so that every refusal is the same with and without a GPU."""
-        name = self.short_name()
+        """What predict_with_gradient refuses, checked before anything touches the device; returns the BCFHW views.  A tensor on another
+        device is refused without asking whether a device exists, so that every refusal is the same with and without a GPU."""
+        what = f"{self.short_name()} predict_with_gradient"
         if not self._psnr_loss:
-            raise vq_exception(f"{name} predict_with_gradient: this metric has no gradient")
-        if not isinstance(wrt, str) or wrt not in _capi.WRT:
-            raise vq_exception(f'{name} predict_with_gradient: wrt must be "test", "reference" or "both", not {wrt!r}')
-        if not torch.is_tensor(test) or not torch.is_tensor(reference):
-            raise vq_exception(f"{name} predict_with_gradient: test and reference must be torch tensors (files, .yuv and resampled sources "
-                               "have no gradient)")
-        if test.dtype != torch.float32 or reference.dtype != torch.float32:
-            raise vq_exception(f"{name} predict_with_gradient: integer and fp16 inputs are out of scope, test and reference must be float32")
-        if not isinstance(dim_order, str) or len(dim_order) != test.dim() or len(dim_order) != reference.dim():
-            raise vq_exception(f'{name} predict_with_gradient: the tensors must have as many dimensions as there are characters in "dim_order"')
-        t = reshuffle_dims(test.detach(), dim_order, "BCFHW")
-        r = reshuffle_dims(reference.detach(), dim_order, "BCFHW")
-        if t.shape[1] != 3 or r.shape[1] != 3:
-            raise vq_exception(f"{name} predict_with_gradient: 1-channel content is out of scope, the gradient is that of three colour channels")
-        if t.shape[0] != r.shape[0]:
-            raise vq_exception(f"{name} predict_with_gradient: test has batch size {t.shape[0]}, reference {r.shape[0]}: they must be equal")
-        if tuple(t.shape) != tuple(r.shape):
-            raise vq_exception(f"{name} predict_with_gradient: the reference must have the test's shape")
-        if t.shape[2] > 1 and not frames_per_second > 0:
-            raise vq_exception(f"{name} predict_with_gradient: a video needs frames_per_second (more than one frame was passed)")
+            raise vq_exception(f"{what}: this metric has no gradient")
+        check_wrt(what, wrt)
+        check_float32_tensors(what, test, reference, " (files, .yuv and resampled sources have no gradient)")
+        t, r = bcfhw_views(what, test, reference, dim_order)
+        check_same_clip(what, t, r, frames_per_second, "the gradient is that of three colour channels")
         if t.device != self.device or r.device != self.device:
-            raise vq_exception(f"{name} predict_with_gradient: host tensors are out of scope, test and reference must be tensors on {self.device}")
+            raise vq_exception(f"{what}: host tensors are out of scope, test and reference must be tensors on {self.device}")
         return t, r
 
     def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0, wrt="test"):
@@ -93,12 +54,7 @@ class psnr_gradient:
         vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
         vs, H, W, N, B, is_yuv, raw, h, args, max_I = self._open(vs)
         code = _capi.WRT[wrt]
-        grads, views = {}, {}
-        for side, tensor in (("test", test), ("reference", reference)):
-            if wrt in (side, "both"):
-                grads[side] = torch.empty(tensor.shape, dtype=torch.float32, device=self.device)
-                views[side] = reshuffle_dims(grads[side], dim_order, "BCFHW")     # a view: the kernel writes the caller's layout
-                assert views[side].untyped_storage().data_ptr() == grads[side].untyped_storage().data_ptr()
+        out = GradOut(test, reference, dim_order, wrt, self.device)
         mse = torch.zeros(B, dtype=torch.float64, device=self.device)
         lib = _capi.lib()
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -111,22 +67,12 @@ class psnr_gradient:
             a = 0
             for tb, rb, dt, fmt, C, n in self._blocks(vs, H, W, N, B, is_yuv, raw, args):
                 st, sr = self._strides(tb, rb, B)
-
-                def out(side):
-                    if side not in views:
-                        return None, None, 0
-                    g = views[side][:, :, a:a + n]
-                    first = (g.data_ptr() - grads[side].data_ptr()) // 4
-                    return g.data_ptr(), (ctypes.c_int64 * 5)(*g.stride()), (grads[side].numel() - first) * 4
-
                 rc = lib.cvvdp_pixel_psnr_gradient(h, code, tb.data_ptr(), st, rb.data_ptr(), sr, B, C, n, H, W, ctypes.byref(args),
-                                                   mse.data_ptr(), *(out("test") + out("reference")), stream)
+                                                   mse.data_ptr(), *out.args("test", a, n), *out.args("reference", a, n), stream)
                 _capi.check(h, rc, "cvvdp_pixel_psnr_gradient")
                 a += n
         psnr = psnr.to(torch.float32)
-        if wrt == "both":
-            return psnr, grads["test"], grads["reference"]
-        return psnr, grads["test" if wrt == "test" else "reference"]
+        return (psnr,) + out.result() if wrt == "both" else (psnr, out.result())
 
     def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, wrt="test"):
         """-psnr [B] (dB; lower is better) attached to autograd through one torch.autograd.Function: backward() multiplies the
@@ -136,4 +82,5 @@ class psnr_gradient:
         self._psnr_gradient_inputs(test, reference, dim_order, frames_per_second, wrt)
         if wrt == "test" and reference.requires_grad:
             raise vq_exception(f'{self.short_name()} differentiable_loss: the reference asks for a gradient, which wrt = "reference" or "both" gives')
-        return _PsnrLoss.apply(test, reference, self, dim_order, frames_per_second, wrt)
+        predict = lambda: self.predict_with_gradient(test, reference, dim_order, frames_per_second, wrt=wrt)
+        return PixelLoss.apply(test, reference, predict, 0.0, dim_order, wrt)

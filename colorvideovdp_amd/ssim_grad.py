@@ -18,25 +18,9 @@ import ctypes
 import torch
 
 from . import _capi
-from .video_source import reshuffle_dims, video_source_array
+from ._pixel_grad import GradOut, PixelLoss, bcfhw_views, check_float32_tensors, check_same_clip, check_wrt
+from .video_source import video_source_array
 from .vq_metric import vq_exception
-
-
-class _ScoreLoss(torch.autograd.Function):
-    """1 - score with the gradient of predict_with_gradient (differentiable_loss)."""
-
-    @staticmethod
-    def forward(ctx, test, reference, metric, dim_order, frames_per_second, wrt):
-        score, grad = metric.predict_with_gradient(test, reference, dim_order, frames_per_second, wrt=wrt)
-        ctx.save_for_backward(*(grad if wrt == "both" else (grad,)))
-        ctx.wrt = wrt
-        return 1.0 - score
-
-    @staticmethod
-    def backward(ctx, upstream):
-        out = [-g * upstream for g in ctx.saved_tensors]
-        g_test, g_ref = {"test": (out[0], None), "reference": (None, out[0])}.get(ctx.wrt) or out
-        return g_test, g_ref, None, None, None, None
 
 
 class ssim_gradient:
@@ -45,31 +29,16 @@ class ssim_gradient:
 
     def _gradient_inputs(self, test, reference, dim_order, frames_per_second, wrt):
         """What predict_with_gradient refuses, checked before anything touches the device; returns the BCFHW views."""
-        name = self.short_name()
-        if not isinstance(wrt, str) or wrt not in _capi.WRT:
-            raise vq_exception(f'{name} predict_with_gradient: wrt must be "test", "reference" or "both", not {wrt!r}')
-        if not torch.is_tensor(test) or not torch.is_tensor(reference):
-            raise vq_exception(f"{name} predict_with_gradient: test and reference must be torch tensors (files, .yuv and resampled sources "
-                               "have no gradient)")
-        if test.dtype != torch.float32 or reference.dtype != torch.float32:
-            raise vq_exception(f"{name} predict_with_gradient: integer and fp16 inputs are out of scope, test and reference must be float32")
-        if not isinstance(dim_order, str) or len(dim_order) != test.dim() or len(dim_order) != reference.dim():
-            raise vq_exception(f'{name} predict_with_gradient: the tensors must have as many dimensions as there are characters in "dim_order"')
-        t = reshuffle_dims(test.detach(), dim_order, "BCFHW")
-        r = reshuffle_dims(reference.detach(), dim_order, "BCFHW")
-        if t.shape[1] != 3 or r.shape[1] != 3:
-            raise vq_exception(f"{name} predict_with_gradient: 1-channel content is out of scope, luma is taken from three colour channels")
-        if t.shape[0] != r.shape[0]:
-            raise vq_exception(f"{name} predict_with_gradient: test has batch size {t.shape[0]}, reference {r.shape[0]}: they must be equal")
-        if tuple(t.shape) != tuple(r.shape):
-            raise vq_exception(f"{name} predict_with_gradient: the reference must have the test's shape")
-        if t.shape[2] > 1 and not frames_per_second > 0:
-            raise vq_exception(f"{name} predict_with_gradient: a video needs frames_per_second (more than one frame was passed)")
+        what = f"{self.short_name()} predict_with_gradient"
+        check_wrt(what, wrt)
+        check_float32_tensors(what, test, reference, " (files, .yuv and resampled sources have no gradient)")
+        t, r = bcfhw_views(what, test, reference, dim_order)
+        check_same_clip(what, t, r, frames_per_second, "luma is taken from three colour channels")
         self._refuse_size("predict_with_gradient", t.shape[3], t.shape[4])
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device available: colorvideovdp_amd has no CPU path")
         if t.device != self.device or r.device != self.device:
-            raise vq_exception(f"{name} predict_with_gradient: test and reference must be tensors on {self.device}")
+            raise vq_exception(f"{what}: test and reference must be tensors on {self.device}")
         return t, r
 
     def predict_with_gradient(self, test, reference, dim_order="BCFHW", frames_per_second=0, wrt="test"):
@@ -85,12 +54,7 @@ class ssim_gradient:
         vs = video_source_array(t, r, frames_per_second, dim_order="BCFHW", display_photometry=self.display_photometry)
         vs, H, W, N, B, is_yuv, raw, h, pargs, _ = self._open(vs, self._refuse)
         code = _capi.WRT[wrt]
-        grads, views = {}, {}
-        for side, tensor in (("test", test), ("reference", reference)):
-            if wrt in (side, "both"):
-                grads[side] = torch.empty(tensor.shape, dtype=torch.float32, device=self.device)
-                views[side] = reshuffle_dims(grads[side], dim_order, "BCFHW")     # a view: the kernel writes the caller's layout
-                assert views[side].untyped_storage().data_ptr() == grads[side].untyped_storage().data_ptr()
+        out = GradOut(test, reference, dim_order, wrt, self.device)
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
         per_frame = self._grad_scratch_per_frame(code, B, H, W)
         lib = _capi.lib()
@@ -99,18 +63,9 @@ class ssim_gradient:
             a = 0
             for tb, rb, dt, fmt, C, n in self._blocks(vs, H, W, N, B, is_yuv, raw, pargs, per_frame):
                 st, sr = self._strides(tb, rb, B)
-
-                def out(side):
-                    if side not in views:
-                        return None, None, 0
-                    g = views[side][:, :, a:a + n]
-                    first = (g.data_ptr() - grads[side].data_ptr()) // 4
-                    return g.data_ptr(), (ctypes.c_int64 * 5)(*g.stride()), (grads[side].numel() - first) * 4
-
-                self._grad_block(lib, h, code, tb, st, rb, sr, B, n, N, H, W, pargs, acc, out("test") + out("reference"), stream)
+                self._grad_block(lib, h, code, tb, st, rb, sr, B, n, N, H, W, pargs, acc, out.args("test", a, n) + out.args("reference", a, n), stream)
                 a += n
-        score = (acc[0] / N).to(torch.float32)
-        return score, ((grads["test"], grads["reference"]) if wrt == "both" else grads["test" if wrt == "test" else "reference"])
+        return (acc[0] / N).to(torch.float32), out.result()
 
     def differentiable_loss(self, test, reference, dim_order="BCFHW", frames_per_second=0, wrt="test"):
         """1 - score as a 0-dim tensor attached to autograd through one torch.autograd.Function: backward() multiplies the gradient of
@@ -118,4 +73,5 @@ class ssim_gradient:
         well).  Inputs and refusals are those of predict_with_gradient."""
         if wrt == "test" and torch.is_tensor(reference) and reference.requires_grad:
             raise vq_exception(f'{self.short_name()} differentiable_loss: the reference asks for a gradient, which wrt = "reference" or "both" gives')
-        return _ScoreLoss.apply(test, reference, self, dim_order, frames_per_second, wrt)
+        predict = lambda: self.predict_with_gradient(test, reference, dim_order, frames_per_second, wrt=wrt)
+        return PixelLoss.apply(test, reference, predict, 1.0, dim_order, wrt)
